@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Obj-GAN image_generation G+D training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one full iteration of the reference's training loop (reference
 image_generation/trainer.py:357-472) on one synthetic COCO-shaped minibatch: three-stage G_NET
@@ -13,7 +13,12 @@ the reference).  Per-GPU batch 16; under
 environment bench.py starts the N ranks itself) every rank steps its own batches and gradients are
 all-reduced: weak scaling, value = N * 16 * steps / time.  Every step gets a new minibatch.
 
-One JSON line is printed by rank 0: the contract fields plus
+A plain run sets up, runs W untimed and K timed steps, and prints one JSON line from rank 0 with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).  `--dump-outputs DIR`
+writes what the last timed step returned (losses, fake images, Inception-score predictions) as DIR/<name>.npy; the
+inputs, weights and random draws are seeded, so that runs with the same arguments can be compared output for output.
+`--full` adds to the line what the headline does not need, each measured after it (a --full run is planned to end
+within FULL_BUDGET_S of its start):
   roofline      the dominant kernel instance (the MFMA implicit-GEMM conv with the largest share
                 of the step): algorithmic flops of its launches / their hipEvent-measured duration
                 (events recorded by the library on the launch stream, in a second untimed pass so
@@ -24,7 +29,8 @@ One JSON line is printed by rank 0: the contract fields plus
                 batch 16 (~90 s each; child process with a hard time limit, batch-8 fallback).  The unmodified
                 reference cannot run on the GPU box (no /root/reference there): `reference_vs_port` carries the
                 reference-vs-port timing measured in the build container (tools/cpu_ref_vs_port.py)
-  side_configs  (default N = 1 run only) two short side records measured after the headline, not the metric: the same
+  kernel_breakdown, conv_total, host_step   the other figures of that second pass and a host-issue probe of one step
+  side_configs  (N = 1 only) short side records measured after the headline, not the metric: the same
                 step on the true fp32 MFMA, and BASELINE config 5 (bf16 mixed precision, batch 32)
   comm          (data-parallel runs) what the gradient exchange moved and what it cost: bytes all-reduced per step,
                 collectives per step, time the compute stream stood still waiting for them, stand-alone all-reduce
@@ -34,8 +40,11 @@ import argparse
 import ctypes
 import json
 import os
+import random
 import sys
 import time
+
+_START = time.perf_counter()
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "obj-gan_amd")):
@@ -77,6 +86,10 @@ def cat_names(math):
 
 
 PMC_TRAFFIC_JSON = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+# a --full run ends within ten minutes: its side configurations stop CPU_BASELINE_MIN_S before FULL_BUDGET_S (seconds from
+# the start of the process), and the CPU baseline's time limits fit what is left
+FULL_BUDGET_S = 540
+CPU_BASELINE_MIN_S = 300
 
 
 def csrc_hash():
@@ -227,6 +240,8 @@ def cpu_baseline(sample_batch=16, timed_steps=3, timeout_s=630):
     should the timed steps not fit the limit, the un-warmed one is reported and says so)."""
     import subprocess
     threads = max(1, min(128, (os.cpu_count() or 2) // 2))
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():     # a host that grants this process fewer cores says so here
+        threads = max(1, min(threads, int(os.environ["OMP_NUM_THREADS"])))
     env = dict(os.environ, OMP_NUM_THREADS=str(threads), MKL_NUM_THREADS=str(threads),
                HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     note = ""
@@ -257,22 +272,27 @@ def cpu_baseline(sample_batch=16, timed_steps=3, timeout_s=630):
             "sample": note}
 
 
-def side_configs(steps=6, warmup=2, timeout_s=240):
-    """Five short side records of the default N = 1 run, each a child `bench.py` on the same GPU after the headline is
-    measured (they are NOT the metric): the same step on the true fp32 MFMA (`--math fp32`, the arithmetic of rounds
-    1-2), on the bf16 MFMA with exactly split operands (`--math bf16x3`, round 3's), BASELINE config 5
+def side_configs(steps=6, warmup=2, timeout_s=240, deadline=None):
+    """Five short side records of the N = 1 `--full` run, each a child `bench.py --full` on the same GPU after the
+    headline is measured (they are NOT the metric): the same step on the true fp32 MFMA (`--math fp32`, the arithmetic of
+    rounds 1-2), on the bf16 MFMA with exactly split operands (`--math bf16x3`, round 3's), BASELINE config 5
     (`--math bf16 --batch 32`: bf16 matrix-core inputs, fp32 accumulation), and the default step with every minibatch
-    crossing PCIe inside the timed region (`--host-batches`: the reference's host hand-over, prefetched)."""
+    crossing PCIe inside the timed region (`--host-batches`: the reference's host hand-over, prefetched).  No child
+    outlives `deadline` (time.perf_counter() seconds); one that would start with less than 30 s left is not started."""
     import subprocess
     out = {}
     for key, extra in (("fp32_mfma_b16", ["--math", "fp32"]), ("bf16x3_b16", ["--math", "bf16x3"]),
                        ("config5_bf16_b32", ["--math", "bf16", "--batch", "32"]),
                        ("pcie_inclusive_b16", ["--host-batches", "--no-kernel-timing"]),
                        ("jpeg_input_b16", ["--jpeg-input", "--no-kernel-timing"])):
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(steps), "--warmup", str(warmup),
                "--no-cpu-baseline", "--no-side-configs"] + extra
+        limit = timeout_s if deadline is None else min(timeout_s, deadline - time.perf_counter())
+        if limit < 30:
+            out[key] = {"error": "not run: the time budget of --full is spent"}
+            continue
         try:
-            txt = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=timeout_s).stdout.decode()
+            txt = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=limit).stdout.decode()
             line = [ln for ln in txt.splitlines() if ln.startswith("{")][-1]
             r = json.loads(line)
             out[key] = {k: r.get(k) for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype")}
@@ -440,10 +460,12 @@ def standalone_allreduce(tr, device, barrier, reps=3):
     return {"standalone_allreduce_ms": ms, "arena_bytes": nbytes}
 
 
-def timed_passes(step, barrier, max_over_ranks, steps, warmup, prof_steps, prof_begin=None, prof_end=None):
+def timed_passes(step, barrier, max_over_ranks, steps, warmup, prof_steps, prof_begin=None, prof_end=None,
+                 after_timed=None):
     """The measurement protocol, on EVERY rank alike (a step holds collectives under data parallelism, so no
     pass may run on a subset of the ranks): `warmup` untimed steps; exactly `steps` steps bracketed by
-    barrier + device synchronize on both sides, the MAX over ranks of that time; then a second, UNTIMED pass
+    barrier + device synchronize on both sides, the MAX over ranks of that time; `after_timed(out)` with what the
+    last timed step returned; then a second, UNTIMED pass
     of `prof_steps` steps during which rank 0 brackets every conv launch with hipEvents on its stream and every
     rank books its collectives (`prof_begin` / `prof_end`) -- the headline carries no event overhead.
     -> (seconds of the timed pass, seconds per step of the profiling pass or None)"""
@@ -451,10 +473,13 @@ def timed_passes(step, barrier, max_over_ranks, steps, warmup, prof_steps, prof_
         step()
     barrier()
     t0 = time.perf_counter()
+    out = None
     for _ in range(steps):
-        step()
+        out = step()
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    if after_timed is not None:
+        after_timed(out)
     prof_dt = None
     if prof_steps > 0:
         if prof_begin is not None:
@@ -469,6 +494,33 @@ def timed_passes(step, barrier, max_over_ranks, steps, warmup, prof_steps, prof_
     return dt, prof_dt
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, path, budget=DUMP_BUDGET_BYTES):
+    """What train_step returned (the discriminator and generator losses, the KL term, the fake images of every branch,
+    the Inception-score monitor's predictions) -> path/<name>.npy in float32.  Above `budget` bytes in all, every array
+    keeps the same share of its elements, drawn with a fixed seed (flattened, ascending index order)."""
+    import numpy as np
+    arrays = {}
+    for k in sorted(out):
+        v = out[k]
+        if torch.is_tensor(v):
+            arrays[k] = v
+        elif isinstance(v, (list, tuple)):
+            arrays.update(("%s_%d" % (k, i), t) for i, t in enumerate(v) if torch.is_tensor(t))
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if total > budget:
+            keep = max(1, a.size * (budget - 4 * len(arrays)) // total)     # (room for the one kept of a small array)
+            idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-baseline-worker":
         return _cpu_baseline_worker(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
@@ -477,6 +529,12 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 16; 32 with --math bf16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: the profiling pass (roofline, kernel "
+                         "breakdown, --shape-table), the host-issue probe, the gradient-exchange pass of data-parallel "
+                         "runs, the side configurations and the CPU baseline (the --no-* options below trim this)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-steps", type=int, default=3,
                     help="timed CPU steps after the warm-up step (default 3, SURVEY.md 8d; 0: report the un-warmed "
@@ -513,6 +571,10 @@ def main():
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 16
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_table and not args.full:
+        ap.error("--shape-table is written by the profiling pass of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_respawn_under_torchrun(args.gpus))
@@ -532,6 +594,7 @@ def main():
     import synth_batch
     from objgan_hip import _lib, ops
     ops.set_conv_math(args.math)
+    random.seed(1234)                               # the class permutations of the discriminators: same every run
     tr = build_trainer(device, args.batch, seed=1234, with_is_monitor=not args.no_is_monitor,
                        workload=args.workload)
     if args.d_streams is not None:
@@ -685,8 +748,9 @@ def main():
     lib = _lib.load()
     from objgan_hip import graphs
     graphs_on = graphs.enabled()
-    timing = (rank == 0) and not args.no_kernel_timing
-    prof_steps = 0 if args.no_kernel_timing else max(1, min(args.steps, 10))
+    kernel_timing = args.full and not args.no_kernel_timing
+    timing = (rank == 0) and kernel_timing
+    prof_steps = max(1, min(args.steps, 10)) if kernel_timing else 0
     timed_streams = int(tr.d_streams)
 
     def prof_begin():
@@ -702,8 +766,11 @@ def main():
             lib.objgan_prof_enable(0)
         graphs.enable(graphs_on)
         tr.d_streams = timed_streams
+    def after_timed(out):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(out, args.dump_outputs)
     dt, prof_dt = timed_passes(step, barrier, max_over_ranks, args.steps, args.warmup, prof_steps,
-                               prof_begin if timing else None, prof_end if timing else None)
+                               prof_begin if timing else None, prof_end if timing else None, after_timed)
     comm = None
     if use_dist and prof_steps > 0:
         # third, untimed pass on EVERY rank alike, in the stream configuration of the timed pass (the collectives are
@@ -721,7 +788,7 @@ def main():
     # host-side cost of a step: with the queue empty, the time the host needs to ISSUE one step (it does not wait for
     # the device) and the time the device still needs afterwards.  host_issue close to ms_per_step = launch-bound.
     host = None
-    if not args.no_kernel_timing:
+    if kernel_timing:
         barrier()
         tr.phase_events = []
         t0 = time.perf_counter()
@@ -870,12 +937,16 @@ def main():
             except Exception:                                   # noqa: BLE001 (CPU build / gloo)
                 comm["rccl_version"] = None
             res["comm"] = comm
-        if (world == 1 and not use_dist and not args.no_side_configs and not args.no_cpu_baseline
+        deadline = _START + FULL_BUDGET_S
+        want_cpu = args.full and world == 1 and not args.no_cpu_baseline and args.workload == "stage3_obj"
+        if (args.full and world == 1 and not use_dist and not args.no_side_configs and not args.no_cpu_baseline
                 and args.workload == "stage3_obj" and args.math == "fp16x2" and args.batch == 16):
-            res["side_configs"] = side_configs()
-        if world == 1 and not args.no_cpu_baseline and args.workload == "stage3_obj":
+            res["side_configs"] = side_configs(deadline=deadline - (CPU_BASELINE_MIN_S if want_cpu else 0))
+        if want_cpu:
+            # the batch-16 attempt and the batch-8 fallback together (4/3 of the first limit) fit what is left
+            left = int(0.75 * (deadline - time.perf_counter()))
             res["cpu_baseline"] = cpu_baseline(timed_steps=args.cpu_baseline_steps,
-                                               timeout_s=300 + 110 * args.cpu_baseline_steps)
+                                               timeout_s=max(30, min(300 + 110 * args.cpu_baseline_steps, left)))
         print(json.dumps(res), flush=True)
     if use_dist:
         dist.destroy_process_group()

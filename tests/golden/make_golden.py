@@ -1,6 +1,6 @@
 """Generate tests/golden/*.pt from the UNMODIFIED reference (run in the build container only):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--shp | --rnn | --standalone]
 
 Inputs are NOT stored: they come from obj-gan_amd/synth_batch.py (seeded, identical everywhere);
 weights are NOT stored: they come from oracle.ref_harness.seeded_state_ (filled by state-dict key).
@@ -176,11 +176,54 @@ def main():
                         out=roi.reference_forward(feat, rois, 6, 6, 1 / 16.0))
 
 
+def make_standalone_golden():
+    """What the CPU tests compared against the reference tree itself -> tests/golden/roi_align_ref_trials.npz (the
+    reference's ROIAlignForwardCpu on twelve seeded trials, inputs included) and tests/golden/reference_host_ref.json
+    (state-dict key -> shape of the five trained networks; the Inception-score helpers on seeded class posteriors)."""
+    import json
+    from oracle import roi
+    roi.build()
+    rng = np.random.RandomState(3)
+    arrs = {}
+    for trial in range(12):
+        H, W = rng.randint(4, 40), rng.randint(4, 40)
+        feat = rng.randn(3, 4, H, W).astype(np.float32)
+        rois = np.zeros((24, 5), np.float32)
+        rois[:, 0] = rng.randint(0, 3, 24)
+        sc = [1 / 16., 1.0, 0.5][trial % 3]
+        xy = rng.uniform(-5, W / sc, (24, 2)); wh = rng.uniform(0, W / sc, (24, 2))
+        rois[:, 1:3] = xy; rois[:, 3:5] = xy + wh
+        if trial % 2 == 0:
+            rois[:, 1:] = np.round(rois[:, 1:])
+        ah, aw = [(6, 6), (2, 2), (7, 5)][trial % 3]
+        arrs.update({"feat%d" % trial: feat, "rois%d" % trial: rois, "pooled%d" % trial: np.array([ah, aw]),
+                     "scale%d" % trial: np.float32(sc), "out%d" % trial: roi.reference_forward(feat, rois, ah, aw, sc)})
+    np.savez_compressed(os.path.join(HERE, "roi_align_ref_trials.npz"), **arrs)
+
+    ref = rh.load_reference(3, 2)
+    M = ref.model
+    nets = {"G_NET": M.G_NET(80), "PAT_D_NET64": M.PAT_D_NET64(), "SHP_D_NET256": M.SHP_D_NET256(80),
+            "OBJ_SS_D_NET": M.OBJ_SS_D_NET(80), "OBJ_LS_D_NET": M.OBJ_LS_D_NET(80)}
+    logits = np.random.RandomState(0).randn(37, 11)
+    p = np.exp(logits) / np.exp(logits).sum(1, keepdims=True)
+    out = {"state_dict_shapes": {n: {k: list(v.shape) for k, v in m.state_dict().items()} for n, m in nets.items()},
+           "inception_score": {"posteriors": "softmax(RandomState(0).randn(37, 11)), 4 splits",
+                               "compute_inception_score": [float(v) for v in ref.utils.compute_inception_score(p, 4)],
+                               "negative_log_posterior_probability":
+                                   [float(v) for v in ref.utils.negative_log_posterior_probability(p, 4)]}}
+    with open(os.path.join(HERE, "reference_host_ref.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     if "--shp" in sys.argv:
         make_shp_golden()
     elif "--rnn" in sys.argv:
         make_rnn_golden()
+    elif "--standalone" in sys.argv:
+        make_standalone_golden()
     else:
         main()
         make_rnn_golden()
+        make_standalone_golden()

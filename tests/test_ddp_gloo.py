@@ -397,7 +397,7 @@ def _bench_main_worker(rank, world, port, q):
     real_init = dist.init_process_group
     dist.init_process_group = lambda backend=None, rank=None, world_size=None, device_id=None, **k: \
         real_init("gloo", rank=rank, world_size=world_size)
-    sys.argv = ["bench.py", "--gpus", str(world), "--workload", "stage1", "--batch", "2", "--steps", "1",
+    sys.argv = ["bench.py", "--full", "--gpus", str(world), "--workload", "stage1", "--batch", "2", "--steps", "1",
                 "--warmup", "1", "--no-is-monitor"]
     out, real_stdout = io.StringIO(), sys.stdout
     sys.stdout = out

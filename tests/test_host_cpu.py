@@ -92,7 +92,8 @@ def test_up_bank_cache_follows_weight_updates():
 
 def test_inception_score_helpers_match_reference(tmp_path):
     """compute_inception_score / negative_log_posterior_probability against the reference's own
-    functions (imported through the oracle harness where /root/reference exists) and a hand value."""
+    functions (their values stored in tests/golden/reference_host_ref.json; the functions themselves, imported through
+    the oracle harness, where the reference tree is present) and a hand value."""
     import numpy as np
     from miscc import utils
     rng = np.random.RandomState(0)
@@ -103,6 +104,12 @@ def test_inception_score_helpers_match_reference(tmp_path):
     uniform = np.full((8, 5), 0.2)
     assert abs(utils.compute_inception_score(uniform, 2)[0] - 1.0) < 1e-12
     assert abs(utils.negative_log_posterior_probability(uniform, 2)[0] - np.log(5.0)) < 1e-12
+    import json
+    import os
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                       "reference_host_ref.json")))["inception_score"]
+    assert np.allclose((m, s), gold["compute_inception_score"], rtol=1e-12, atol=0)
+    assert np.allclose((mc, sc), gold["negative_log_posterior_probability"], rtol=1e-12, atol=0)
     from oracle import ref_harness
     if ref_harness.available():
         ref = ref_harness.load_reference().utils
@@ -308,11 +315,10 @@ def test_gradient_buckets_leave_in_descending_order_whatever_the_completion_orde
     arena._mark(0)                                                            # disarmed: hooks are inert
 
 
-def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
-    """bench.main() from argument parsing to the JSON line, with the kernels replaced by their CPU
-    definitions and the device calls stubbed (stage-1 workload, batch 2, one timed step + the profiling
-    pass): the line carries the contract's fields, the step count of the protocol is right, and the roofline
-    object is derived from the library's per-kernel records (here: two synthetic launches, 100 TFLOP/s)."""
+def _bench_main_on_cpu_shim(monkeypatch, capsys, argv):
+    """bench.main(argv) with the kernels replaced by their CPU definitions and the device calls stubbed (stage-1
+    workload, batch 2); the library's per-kernel records hold two synthetic launches of one kernel instance.
+    -> (the JSON line, the number of train_step calls, the profiling switches the library saw)"""
     import json
     import sys
     import bench
@@ -323,7 +329,8 @@ def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
     cpu_ops_shim.install(monkeypatch)
 
     class FakeLib(object):
-        enabled = []
+        def __init__(self):
+            self.enabled = []
 
         def objgan_prof_enable(self, on):
             self.enabled.append(on)
@@ -342,8 +349,7 @@ def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
     real_step = T.condGANTrainer.train_step
     monkeypatch.setattr(T.condGANTrainer, "train_step",
                         lambda self, *a, **k: (steps.append(1), real_step(self, *a, **k))[1])
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "stage1", "--batch", "2", "--steps", "1",
-                                      "--warmup", "1", "--no-cpu-baseline", "--no-is-monitor"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "stage1", "--batch", "2"] + argv)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     saved = cfg.TREE.BRANCH_NUM
     try:
@@ -351,8 +357,16 @@ def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
     finally:
         cfg.TREE.BRANCH_NUM = saved
     line = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1]
-    res = json.loads(line)
-    assert len(steps) == 1 + 1 + 1 + 1 and fake.enabled == [1, 0]        # warm-up, timed, profiling pass, host-issue probe
+    return json.loads(line), len(steps), fake.enabled
+
+
+def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
+    """bench.main() --full from argument parsing to the JSON line, on the CPU shim (one timed step + the profiling
+    pass): the line carries the contract's fields, the step count of the protocol is right, and the roofline
+    object is derived from the library's per-kernel records (here: two synthetic launches, 100 TFLOP/s)."""
+    res, n_steps, enabled = _bench_main_on_cpu_shim(
+        monkeypatch, capsys, ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-is-monitor"])
+    assert n_steps == 1 + 1 + 1 + 1 and enabled == [1, 0]        # warm-up, timed, profiling pass, host-issue probe
     assert res["host_step"]["issue_ms"] > 0
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
@@ -365,6 +379,49 @@ def test_bench_main_end_to_end_on_the_cpu_shim(monkeypatch, capsys):
     assert roof["traffic"] is None or roof["traffic"] > 1e8             # committed PMC record of that kernel
     assert res["conv_total"]["tflops"] == roof["achieved"] and res["kernel_breakdown"][0]["launches_per_step"] == 2.0
     assert "cpu_baseline" not in res and "side_configs" not in res and res["dtype"].startswith("fp32 (fp16x2")
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_ones_outputs(monkeypatch, capsys, tmp_path):
+    """A plain run (no --full) steps exactly warm-up + timed steps, with no profiling pass, and prints the contract
+    fields with ms_per_step = timed time / steps.  --dump-outputs writes what the last timed step returned as float32
+    .npy files; a second run with the same arguments writes the same arrays (seeded inputs, weights and draws)."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        res, n_steps, enabled = _bench_main_on_cpu_shim(
+            monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--no-is-monitor", "--dump-outputs", str(d)])
+        assert n_steps == 1 + 2 and enabled == []
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["higher_is_better"] is True
+        assert abs(res["value"] - 2 * 1000.0 / res["ms_per_step"]) < 1e-3 * res["value"]
+        for k in ("metric", "unit", "dtype"):
+            assert res[k]
+        for k in ("roofline", "kernel_breakdown", "conv_total", "host_step", "side_configs", "cpu_baseline", "comm"):
+            assert k not in res
+        dumps.append({f.name: np.load(str(f)) for f in sorted(d.iterdir())})
+    names = set(dumps[0])
+    assert {"errG.npy", "kl.npy", "fake_imgs_0.npy", "errPatD0.npy"} <= names and set(dumps[1]) == names
+    assert dumps[0]["fake_imgs_0.npy"].shape == (2, 3, 64, 64)
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for n in names:
+        assert dumps[0][n].dtype == np.float32 and np.all(np.isfinite(dumps[0][n]))
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+def test_bench_dump_outputs_samples_above_the_budget(tmp_path):
+    """Above the byte budget every array keeps the same share of its elements, drawn with a fixed seed."""
+    import numpy as np
+    import bench
+    out = {"big": torch.arange(4000, dtype=torch.float32).reshape(40, 100), "loss": torch.tensor(1.5),
+           "imgs": [torch.ones(2, 3), torch.zeros(10, dtype=torch.float64)]}
+    for run in range(2):
+        names = bench.dump_outputs(out, str(tmp_path / str(run)), budget=4 * 1000)
+        assert names == ["big", "imgs_0", "imgs_1", "loss"]
+    a, b = (np.load(str(tmp_path / r / "big.npy")) for r in ("0", "1"))
+    assert np.array_equal(a, b) and a.dtype == np.float32 and a.ndim == 1 and a.size == 4000 * (4000 - 4 * 4) // (4 * 4017)
+    assert np.all(np.diff(a) > 0)                    # distinct elements of the flattened array, in index order
+    assert sum(np.load(str(f)).nbytes for f in (tmp_path / "0").iterdir()) <= 4 * 1000
+    assert np.load(str(tmp_path / "0" / "loss.npy")).shape == (1,)
 
 
 def test_bench_respawn_passes_every_flag_through_and_numa_slices_are_disjoint():

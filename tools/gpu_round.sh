@@ -5,6 +5,7 @@ set -x
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-run}; shift
+OUT=${OUT:-out}; mkdir -p "$OUT"     # logs and tables of the --full bench runs below
 R=$GRAFT_REPO_ROOT
 for what in "$@"; do case $what in
 test) rm -f gpurun_out/parity_numbers.txt
@@ -12,12 +13,12 @@ test) rm -f gpurun_out/parity_numbers.txt
   cp gpurun_out/parity_numbers.txt gpurun_out/${TAG}_parity.txt 2>/dev/null ;;
 testk) ( time timeout 900 python -m pytest tests -m gpu -x -v --timeout=240 --durations=10 -k "$OG_K" ) > gpurun_out/${TAG}_pytestk.log 2>&1; tail -15 gpurun_out/${TAG}_pytestk.log ;;
 convbench) ( timeout 300 tools/conv_bench "" 5 ) > gpurun_out/${TAG}_convbench.log 2>&1; cat gpurun_out/${TAG}_convbench.log ;;
-bench) ( time timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --shape-table gpurun_out/${TAG}_shapes.txt ) > gpurun_out/${TAG}_bench.log 2>&1; tail -3 gpurun_out/${TAG}_bench.log ;;
-benchfull) ( time timeout 1700 python bench.py --steps 20 --warmup 5 --shape-table gpurun_out/${TAG}_conv_shapes.txt ) > gpurun_out/${TAG}_benchfull.log 2>&1; tail -3 gpurun_out/${TAG}_benchfull.log ;;
-benchddp) ( time timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --force-ddp ) > gpurun_out/${TAG}_benchddp.log 2>&1; tail -3 gpurun_out/${TAG}_benchddp.log ;;
+bench) ( time timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --shape-table $OUT/${TAG}_shapes.txt ) > $OUT/${TAG}_bench.log 2>&1; tail -3 $OUT/${TAG}_bench.log ;;
+benchfull) ( time timeout 1700 python bench.py --full --steps 20 --warmup 5 --shape-table $OUT/${TAG}_conv_shapes.txt ) > $OUT/${TAG}_benchfull.log 2>&1; tail -3 $OUT/${TAG}_benchfull.log ;;
+benchddp) ( time timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --force-ddp ) > $OUT/${TAG}_benchddp.log 2>&1; tail -3 $OUT/${TAG}_benchddp.log ;;
 benchbf16) ( time timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --math bf16 --batch 32 ) > gpurun_out/${TAG}_benchbf16.log 2>&1; tail -3 gpurun_out/${TAG}_benchbf16.log | cut -c1-600 ;;
 benchcfg) for w in stage3 stage1; do ( time timeout 300 python bench.py --steps 8 --warmup 2 --workload $w ) > gpurun_out/${TAG}_bench_$w.log 2>&1; tail -3 gpurun_out/${TAG}_bench_$w.log | cut -c1-700; done ;;
-bench8t) ( time timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --shape-table gpurun_out/${TAG}_conv_shapes.txt ) > gpurun_out/${TAG}_bench8t.log 2>&1; tail -3 gpurun_out/${TAG}_bench8t.log | cut -c1-400 ;;
+bench8t) ( time timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --shape-table $OUT/${TAG}_conv_shapes.txt ) > $OUT/${TAG}_bench8t.log 2>&1; tail -3 $OUT/${TAG}_bench8t.log | cut -c1-400 ;;
 bench8) ( time timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline ) > gpurun_out/${TAG}_bench8.log 2>&1; tail -3 gpurun_out/${TAG}_bench8.log | cut -c1-400 ;;
 smoke) ( timeout 300 python __graft_entry__.py --smoke ) > gpurun_out/${TAG}_smoke.log 2>&1; tail -2 gpurun_out/${TAG}_smoke.log ;;
 pmcstep) bash tools/pmc_step.sh ${TAG} > gpurun_out/${TAG}_pmcstep.log 2>&1; tail -3 gpurun_out/${TAG}_pmcstep.log ;;
