@@ -15,7 +15,7 @@
 // Records are written by objgan_h2_records (one pass: 4 B read + 4 B written per element) or by the producer of the
 // tensor itself (norm.hip apply kernels).  Reference: the convolutions of image_generation/model.py:30-81, 589-617,
 // 986-1048, 1184-1312, which the reference hands to cuDNN.
-#include "conv_igemm3.h"
+#include "conv_igemm_host.h"
 
 // fp32 [N][C][HW] -> records [N][Cp/16][2][HW][16]; 64 channels x 64 pixels per workgroup through LDS
 // (256-byte rows in, 1 KiB runs per wave and piece out).
@@ -56,31 +56,22 @@ __global__ __launch_bounds__(256) void h2_records_kernel(const float* __restrict
     }
 }
 
-// launch of the record-reading instances (called by run_igemm2 in conv_igemm.hip)
+// launch of the record-reading instances (called by launch_igemm2 in conv_igemm.hip)
 int og_launch_igemm3_rec(const IgemmArgs& a, int TM, int nw, int ng, dim3 grid, hipStream_t s) {
-#define OG_REC(TMv, NGv)                                                                                              \
-        if (nw == 8) hipLaunchKernelGGL((conv_igemm3_kernel<TMv, false, 5, 8, NGv>), grid, dim3(512), 0, s, a);       \
-        else hipLaunchKernelGGL((conv_igemm3_kernel<TMv, false, 5, 4, NGv>), grid, dim3(256), 0, s, a);
     if (ng == 2) {
-        switch (TM) {
-            case 1: OG_REC(1, 2) break;
-            case 2: OG_REC(2, 2) break;
-            case 3: OG_REC(3, 2) break;
-            case 4: OG_REC(4, 2) break;
-            default: return OG_BAD_ARGS;
-        }
+        if (TM < 1 || TM > 4) return OG_BAD_ARGS;           // two pixel groups per wave: block rows up to 4 groups
+        og_with_tm<1, 4>(TM, [&](auto tmc) {
+            constexpr int T = decltype(tmc)::value;
+            if (nw == 8) hipLaunchKernelGGL((conv_igemm3_kernel<T, false, 5, 8, 2>), grid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((conv_igemm3_kernel<T, false, 5, 4, 2>), grid, dim3(256), 0, s, a);
+        });
         return og_launch_status();
     }
-    switch (TM) {
-        case 1: OG_REC(1, 1) break;
-        case 2: OG_REC(2, 1) break;
-        case 3: OG_REC(3, 1) break;
-        case 4: OG_REC(4, 1) break;
-        case 5: OG_REC(5, 1) break;
-        case 6: OG_REC(6, 1) break;
-        default: OG_REC(7, 1) break;
-    }
-#undef OG_REC
+    og_with_tm<1, 7>(TM, [&](auto tmc) {                    // (out-of-range heights run the 7-group instance)
+        constexpr int T = decltype(tmc)::value;
+        if (nw == 8) hipLaunchKernelGGL((conv_igemm3_kernel<T, false, 5, 8, 1>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((conv_igemm3_kernel<T, false, 5, 4, 1>), grid, dim3(256), 0, s, a);
+    });
     return og_launch_status();
 }
 
@@ -94,11 +85,11 @@ int og_launch_igemm3_rec(const IgemmArgs& a, int TM, int nw, int ng, dim3 grid, 
 // piece l, 4 loads, every geometry (padding, reflection, stride, upsampling) is just the record address, taken from two
 // small LDS tables -- the wave parks them in a wave-private LDS image [piece][half][16 pixels][2 chunks x 16 channels]
 // and reads them back TRANSPOSED with ds_read_b64_tr_b16 (gfx950): four consecutive pixels of one channel per lane,
-// i.e. the MFMA's B fragment.  The scheme is conv_wgrad_bfb_kernel's (bf16 mode, conv_igemm.hip), with two pieces.
+// i.e. the MFMA's B fragment.  The scheme is conv_wgrad_bfb_kernel's (bf16 mode, conv_igemm_wgrad.hip), with two pieces.
 // dy comes from the fp32 tensor: the loader thread scales and splits its four pixels on the way into LDS (row image
 // [h 32 px | l 32 px], 144-byte pitch).  Products and their order per 16-pixel step as conv_wgrad3_kernel<.., 4>:
 // al.bh, ah.bh, ah.bl with fp32 accumulation; scales undone in the epilogue.
-// Requires OH * OW % 32 == 0, OH, OW <= 256, (H - 1) * W < 65535, k <= 4 (og_wgrad asks objgan_conv_wgrad_rec_ok).
+// Requires OH * OW % 32 == 0, OH, OW <= 256, (H - 1) * W < 65535, k <= 4 (og_wgrad_plan asks og_wgrad_rec_geometry).
 // DYP (round 6): dy ALSO arrives pre-split -- a.dy is the fp16 pair of the tensor in its own NCHW layout, plane h
 // followed by plane l (h2_pair_kernel below, same scale and the same two conversions as the loader's split) -- and
 // the loader threads copy 16-byte pieces (8 pixels of one plane) straight into the same LDS row image: no operand split is
@@ -354,7 +345,7 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_rec_kernel(const WgradArgs
     }
 }
 
-// launch of the record-reading weight gradient (called by og_wgrad in conv_igemm.hip)
+// launch of the record-reading weight gradient (called by objgan_conv_wgrad in conv_igemm_wgrad.hip)
 // ---- weight gradient on records, TWO column groups per wave (round 6) --------------------------------------------------
 // conv_wgrad_rec_kernel above is bound by its LDS fragment reads: per 32-pixel iteration the eight waves of a 192-row tile
 // read 8 x 24 KB of dy row fragments (every wave the same rows, for its own 32 columns) -- ~2 060 cycles at 128 B/clk against
@@ -619,13 +610,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_rec2_kernel(const WgradArgs a,
 }
 
 int og_launch_wgrad_rec2(const WgradArgs& a, int tm, dim3 grid, int ksize, int Cp, hipStream_t s) {
-    switch (tm) {
-        case 1: hipLaunchKernelGGL((conv_wgrad_rec2_kernel<1>), grid, dim3(512), 0, s, a, ksize, Cp); break;
-        case 2: hipLaunchKernelGGL((conv_wgrad_rec2_kernel<2>), grid, dim3(512), 0, s, a, ksize, Cp); break;
-        case 3: hipLaunchKernelGGL((conv_wgrad_rec2_kernel<3>), grid, dim3(512), 0, s, a, ksize, Cp); break;
-        case 4: hipLaunchKernelGGL((conv_wgrad_rec2_kernel<4>), grid, dim3(512), 0, s, a, ksize, Cp); break;
-        default: return OG_BAD_ARGS;
-    }
+    if (tm < 1 || tm > 4) return OG_BAD_ARGS;               // two column groups per wave: block rows up to 4 groups
+    og_with_tm<1, 4>(tm, [&](auto tmc) {
+        hipLaunchKernelGGL((conv_wgrad_rec2_kernel<decltype(tmc)::value>), grid, dim3(512), 0, s, a, ksize, Cp);
+    });
     return og_launch_status();
 }
 
@@ -658,22 +646,15 @@ void og_launch_h2_pair(const float* x, const float* xmax, float* out, long n, hi
 }
 
 int og_launch_wgrad_rec(const WgradArgs& a, int tm, int nw, dim3 grid, int ksize, int Cp, int dyp, hipStream_t s) {
-#define OG_WGR(TMv)                                                                                                   \
-        if (dyp && nw == 8) hipLaunchKernelGGL((conv_wgrad_rec_kernel<(TMv <= 6 ? TMv : 6), 8, true>), grid, dim3(512), 0, s, a, ksize, Cp); \
-        else if (dyp) hipLaunchKernelGGL((conv_wgrad_rec_kernel<TMv, 4, true>), grid, dim3(256), 0, s, a, ksize, Cp); \
-        else if (nw == 8) hipLaunchKernelGGL((conv_wgrad_rec_kernel<(TMv <= 6 ? TMv : 6), 8>), grid, dim3(512), 0, s, a, ksize, Cp); \
-        else hipLaunchKernelGGL((conv_wgrad_rec_kernel<TMv, 4>), grid, dim3(256), 0, s, a, ksize, Cp);
     if (nw == 8 && tm > 6) return OG_BAD_ARGS;
-    switch (tm) {
-        case 1: OG_WGR(1) break;
-        case 2: OG_WGR(2) break;
-        case 3: OG_WGR(3) break;
-        case 4: OG_WGR(4) break;
-        case 5: OG_WGR(5) break;
-        case 6: OG_WGR(6) break;
-        default: OG_WGR(7) break;
-    }
-#undef OG_WGR
+    og_with_tm<1, 7>(tm, [&](auto tmc) {
+        constexpr int T = decltype(tmc)::value;
+        constexpr int T8 = T <= 6 ? T : 6;                  // 8 waves: the LDS of a 7-group row tile does not fit
+        if (dyp && nw == 8) hipLaunchKernelGGL((conv_wgrad_rec_kernel<T8, 8, true>), grid, dim3(512), 0, s, a, ksize, Cp);
+        else if (dyp) hipLaunchKernelGGL((conv_wgrad_rec_kernel<T, 4, true>), grid, dim3(256), 0, s, a, ksize, Cp);
+        else if (nw == 8) hipLaunchKernelGGL((conv_wgrad_rec_kernel<T8, 8, false>), grid, dim3(512), 0, s, a, ksize, Cp);
+        else hipLaunchKernelGGL((conv_wgrad_rec_kernel<T, 4, false>), grid, dim3(256), 0, s, a, ksize, Cp);
+    });
     return og_launch_status();
 }
 
