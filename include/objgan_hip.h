@@ -377,6 +377,23 @@ int objgan_jpeg_decode(const unsigned char* files, const void* descs_host, const
 int objgan_mask_resize(const double* src, int count, int n, int nsizes, const int* sizes, double* const* out,
                        const int* ntaps, const double* taps, void* stream);
 
+/* ---- evaluation statistics on the device (csrc/eval_stats.hip) -------------------------------------------
+ * objgan_bilinear_halfpixel_forward  the input preparation of the FID feature network (reference
+ *     image_generation/model.py:433-441): y[N, C, OH, OW] = F.interpolate(x, (OH, OW), 'bilinear',
+ *     align_corners=False) -- source index max(0, (dst + 0.5) * in / out - 0.5), upper neighbour clamped to in - 1, no
+ *     antialiasing -- then y = y * scale[c] + shift[c] when the two C-float device tables are given (both or neither).
+ * objgan_moments_accumulate  x fp32 [rows, D]: sum[D] += sum_r x[r], outer[D, D] += sum_r x[r]^T x[r] in fp64; only the
+ *     upper triangle of outer (diagonal included) is read and written.  One thread owns each output element and adds
+ *     the rows in row order (no atomics): bit-reproducible, and independent of how a row sequence is cut into calls.
+ *     The caller zeroes sum / outer once.  A call streams the whole accumulator: hand over several batches at a time.
+ * objgan_moments_finalize  mu[D] = sum / n, sigma[D, D] = (outer - n mu mu^T) / (n - 1) (np.cov's normalisation),
+ *     mirrored to the full, exactly symmetric matrix; n >= 2 rows were accumulated. */
+int objgan_bilinear_halfpixel_forward(const float* x, float* y, int N, int C, int H, int W, int OH, int OW,
+                                      const float* scale, const float* shift, void* stream);
+int objgan_moments_accumulate(const float* x, int rows, int D, double* sum, double* outer, void* stream);
+int objgan_moments_finalize(const double* sum, const double* outer, long n, int D, double* mu, double* sigma,
+                            void* stream);
+
 /* ---- measurement aid (bench.py roofline leg): hipEvent-bracketed conv launches ------------------ */
 int objgan_prof_enable(int on);
 int objgan_prof_collect(double* ms, double* flops, long* count);   /* arrays of 192 categories (48..95: fp16x2 instances; 96..191: fp16x2 on records, one / two pixel groups) */

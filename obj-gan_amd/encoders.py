@@ -13,6 +13,8 @@ CPU path here: the plain-PyTorch twin the parity tests compare against lives in
 oracle/torch_encoders.py and exchanges weights with these modules through the state dict.  The bench
 and the parity tests use seeded random weights (no checkpoint can be shipped or downloaded).
 """
+import types
+
 import torch
 import torch.nn as nn
 
@@ -278,3 +280,61 @@ class INCEPTION_V3(nn.Module):
         x = (input * 0.5 + 0.5 - self.mean) / self.std
         x = ops.bilinear_resize(x, 299, 299)
         return ops.softmax_strided(self.model(x), 1)
+
+
+# The four stages of the FID network: `blocks.{0..3}.{position}` in the reference's state dict (its pooling layers sit
+# behind the convolutions of a stage and own no parameters, so the keys agree).
+FID_BLOCKS = (TRUNK_MODULES[0:3], TRUNK_MODULES[3:5], TRUNK_MODULES[5:13], TRUNK_MODULES[13:16])
+
+
+class INCEPTION_V3_FID(nn.Module):
+    """FID feature network (reference model.py:318-451): the Inception-v3 trunk held as `blocks.{0..3}.*`, fed with
+    the half-pixel bilinear 299 x 299 resize and the reference's re-normalisation, returning the pooled 2048-d
+    activations as `[pool3]` of shape [B, 2048, 1, 1].  Resize and affine are one launch
+    (`ops.bilinear_resize_halfpixel` with the two affines of the reference forward folded per channel).  Only output
+    block 3 runs here; the shallower feature maps (64 / 192 / 768-d) are refused."""
+
+    DEFAULT_BLOCK_INDEX = 3
+    BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}
+
+    def __init__(self, output_blocks=(DEFAULT_BLOCK_INDEX,), resize_input=True, trunk=None):
+        super().__init__()
+        self.resize_input = resize_input
+        self.output_blocks = sorted(output_blocks)
+        self.last_needed_block = max(output_blocks)
+        if self.output_blocks != [3]:
+            dims = {v: k for k, v in self.BLOCK_INDEX_BY_DIM.items()}
+            raise NotImplementedError(
+                "INCEPTION_V3_FID: only output block 3 (2048-d pooled features, cfg.TEST.FID_DIMS = 2048) is "
+                "implemented, got blocks %s (%s-d)" % (self.output_blocks, [dims.get(b, "?") for b in self.output_blocks]))
+        net = trunk if trunk is not None else self._load_pretrained()
+        for p in net.parameters():
+            p.requires_grad = False
+        self.blocks = nn.ModuleList()
+        for names in FID_BLOCKS:
+            self.blocks.append(nn.Sequential(*[getattr(net, n) for n in names]))
+        # the same modules under their torchvision names, for `inception_trunk`; not a Module, so no second key set
+        self.trunk = types.SimpleNamespace(**{n: getattr(net, n) for n in TRUNK_MODULES})
+        # (x * 0.5 + 0.5) * a + b with a = std / 0.5, b = (mean - 0.5) / 0.5  ==  x * (0.5 a) + (0.5 a + b)
+        a = torch.tensor([0.229, 0.224, 0.225]) / 0.5
+        b = (torch.tensor([0.485, 0.456, 0.406]) - 0.5) / 0.5
+        self.register_buffer("in_scale", 0.5 * a, persistent=False)
+        self.register_buffer("in_shift", 0.5 * a + b, persistent=False)
+
+    @staticmethod
+    def _load_pretrained():
+        """The torchvision ImageNet state dict next to the DAMSM encoders, like the reference (model.py:367-370)."""
+        from miscc.config import cfg
+        net = inception_v3()
+        path = cfg.TRAIN.NET_E.replace('text_encoder100.pth', 'inception_v3_google-1a9a5a14.pth')
+        net.load_state_dict(torch.load(path, map_location="cpu"))
+        return net
+
+    def forward(self, inp):
+        x = inp
+        if self.resize_input:
+            x = ops.bilinear_resize_halfpixel(x, 299, 299, self.in_scale, self.in_shift)
+        else:
+            x = x * self.in_scale.view(1, 3, 1, 1) + self.in_shift.view(1, 3, 1, 1)
+        pool3 = inception_trunk(self.trunk, x)
+        return [pool3.view(pool3.size(0), -1, 1, 1)]

@@ -7,8 +7,14 @@ with nn.DataParallel:
 
 Under a launcher (WORLD_SIZE in the environment) every rank takes GPU LOCAL_RANK, joins the RCCL
 process group and reads its own shard of every epoch (trainDataset.build_loader); `--BATCH_SIZE` is the
-per-GPU batch.  Without `--FLAG` main() stops with a pointer to evaluator.condGANEvaluator.sampling(): the
-reference's test-set loader and its FID / R-precision bookkeeping are outside the hot path.
+per-GPU batch.
+
+Without `--FLAG` the test split is evaluated on one GPU (reference main.py:126-138):
+
+    python main.py --gpu 0 --data_dir ../data/coco --NET_G <checkpoint> --BATCH_SIZE 16
+
+writes `Image/*.jpg` and `Score/scores.txt` (Inception score, R-precision, FID) under the output directory; the FID
+activations of the real images are computed once and kept in `<data_dir>/test_acts_tf0.pickle`.
 """
 from __future__ import print_function
 
@@ -66,6 +72,11 @@ def parse_args(argv=None):
     parser.add_argument('--device_masks', action='store_true',
                         help='hand over the raw 64 x 64 instance masks and resize them on the device (scipy-exact); '
                              'implies --device_hmaps')
+    parser.add_argument('--USE_GT_BOX_SEG', type=int, choices=(0, 1, 2), default=None,
+                        help='evaluation layout: 0 ground-truth boxes and shapes, 1 ground-truth boxes and generated '
+                             'shapes, 2 generated boxes and shapes (default: cfg.TEST.USE_GT_BOX_SEG)')
+    parser.add_argument('--TEST_IMG_NUM', type=int, default=None,
+                        help='evaluation: stop after this many BATCHES (default: cfg.TEST.TEST_IMG_NUM)')
     return parser.parse_args(argv)
 
 
@@ -93,6 +104,10 @@ def apply_args(args):
     cfg.TRAIN.BATCH_SIZE = args.BATCH_SIZE
     cfg.TREE.BRANCH_NUM = args.BRANCH_NUM
     cfg.TRAIN.FLAG = args.FLAG
+    if getattr(args, "USE_GT_BOX_SEG", None) is not None:
+        cfg.TEST.USE_GT_BOX_SEG = args.USE_GT_BOX_SEG
+    if getattr(args, "TEST_IMG_NUM", None) is not None:
+        cfg.TEST.TEST_IMG_NUM = args.TEST_IMG_NUM
     if args.gpu_ids != '-1':
         cfg.GPU_IDS = [int(gpu_id) for gpu_id in args.gpu_ids.split(',')]
     else:
@@ -160,6 +175,23 @@ def build_training(args, rank, world, device):
     return dataset, dataloader, algo
 
 
+def build_evaluation(args, rank, world, device):
+    """-> (dataset, dataloader, evaluator) for the test split (reference main.py:126-132): in file order, whole
+    batches only."""
+    if world > 1:
+        raise SystemExit("evaluation runs on a single GPU: start main.py without a launcher (WORLD_SIZE=%d)" % world)
+    from testDataset import TestDataset
+    from evaluator import condGANEvaluator
+    timestamp = datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')
+    output_dir = '{0}/output_image_generation/{1}_{2}'.format(args.output_dir, cfg.DATASET_NAME, timestamp)
+    dataset = TestDataset(cfg.DATA_DIR, 'test', base_size=cfg.TREE.BASE_SIZE)
+    assert dataset
+    dataloader = torch.utils.data.DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=False,
+                                             num_workers=int(cfg.WORKERS))
+    algo = condGANEvaluator(output_dir, dataloader, dataset, device=device)
+    return dataset, dataloader, algo
+
+
 def main(argv=None):
     args = parse_args(argv)
     apply_args(args)
@@ -174,8 +206,13 @@ def main(argv=None):
         algo.train()
         split_dir = 'train'
     else:
-        raise SystemExit("the evaluation data pipeline (testDataset, FID / R-precision) is outside the hot path: "
-                         "use evaluator.condGANEvaluator.sampling() on prepared tensors")
+        split_dir = 'test'
+        dataset, _, algo = build_evaluation(args, rank, world, device)
+        if dataset.acts_dict is None:
+            from miscc.load import load_acts_data
+            algo.dump_fid_acts(cfg.DATA_DIR, split_dir)
+            dataset.acts_dict = load_acts_data(cfg.DATA_DIR, split_dir)
+        algo.evaluate(split_dir, dataset.imsize)
     if rank == 0:
         print('Total time for {0}:'.format(split_dir), time.time() - start_t)
     if world > 1:

@@ -338,6 +338,64 @@ def get_hmaps_rois(anno_dict, hmap_size, fmap_size, cats_index_dict, with_hmaps=
     return hmaps, bbox_maps_fwd, bbox_maps_bwd, bbox_fmaps, rois, fm_rois, num_rois, bt_masks, fm_bt_masks
 
 
+def get_gen_rois(anno_dicts, hmap_size, fmap_size, cats_index_dict, sent_ix):
+    """Box slots and box maps of the GENERATED layout of caption `sent_ix` of an image (reference load.py:194-214;
+    `<split>_gen_insanns.pickle` holds one annotation dictionary per caption)."""
+    anno = anno_dicts[sent_ix]
+    rois, fm_rois, num_rois = anno['rois'], anno['fm_rois'], anno['num_rois']
+    R, ncat = cfg.ROI.BOXES_NUM, len(cats_index_dict)
+    bbox_maps_fwd = np.zeros((R, ncat, hmap_size[0], hmap_size[0]))
+    bbox_maps_bwd = np.zeros((R, ncat, hmap_size[0], hmap_size[0]))
+    bbox_fmaps = np.zeros((R, fmap_size, fmap_size))
+    if num_rois > 0 and anno['bbox maps'] is not None:
+        for r in range(num_rois):
+            bbox_maps_fwd[r, int(rois[0][r, 4])] = anno['bbox maps'][r]
+        bbox_maps_bwd = bbox_maps_fwd[::-1].copy()
+        bbox_fmaps[:num_rois] = anno['bbox fmaps']
+    return bbox_maps_fwd, bbox_maps_bwd, bbox_fmaps, rois, fm_rois, num_rois
+
+
+# ---------------------------------------------------------------------------------------------
+# evaluation split
+# ---------------------------------------------------------------------------------------------
+def acts_filename(split):
+    """`<split>_acts_tf<USE_TF>.pickle` with the USE_TF value in effect: there is no TensorFlow route here, so the
+    PyTorch file (`_tf0`) is the only one this package writes or reads."""
+    return '%s_acts_tf%d.pickle' % (split, 0)
+
+
+def load_acts_data(data_dir, split):
+    """{key: float64 (2048,)} FID activations of the real images of a split, or None when the file is missing
+    (reference load.py:465-477; evaluator.dump_fid_acts writes it)."""
+    filepath = os.path.join(data_dir, acts_filename(split))
+    if not os.path.isfile(filepath):
+        print('Error: no such a file %s' % filepath)
+        return None
+    acts_dict = _load_pickle(filepath, encoding='latin1')[0]
+    print('Load from: ', filepath)
+    return acts_dict
+
+
+def load_sample_filenames(data_dir):
+    """`<data_dir>/sample/filenames.txt`, one `name,sentid` per line -> (names, sentence ids), for
+    cfg.TEST.SAMPLE_VAL.  NOT pinned to the reference: its version (load.py:447-463) opens the file in binary mode
+    and calls str.replace on the lines, which raises under Python 3, so there is nothing to compare against; this
+    reads the same lines in text mode."""
+    filepath = '%s/sample/filenames.txt' % data_dir
+    filenames, sentids = [], []
+    if os.path.isfile(filepath):
+        with open(filepath, 'r') as f:
+            lines = [ln.strip() for ln in f.read().splitlines()]
+        print('Load filenames from: %s (%d)' % (filepath, len(lines)))
+        for pair in lines:
+            if not pair:
+                continue
+            name, sentid = pair.split(',')
+            filenames.append(name)
+            sentids.append(int(sentid))
+    return filenames, sentids
+
+
 def install_torchtext_stub():
     """Make `torchtext.vocab.Vocab` resolvable for plain pickle.load callers (tools, tests)."""
     import sys

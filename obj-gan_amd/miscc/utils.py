@@ -1,7 +1,7 @@
 """Hot-path helpers of the image generator (the subset of reference
 image_generation/miscc/utils.py that the G+D training step calls: :309-329, :365-413,
-:445-522).  Visualisation and IS/FID utilities of the reference file are outside the hot-path
-scope and are not provided.
+:445-522) and its Inception-score / FID utilities (:358-362, :417-441, :586-714).  The visualisation
+utilities of the reference file (image grids) are not provided.
 """
 import random
 from copy import deepcopy
@@ -307,3 +307,68 @@ def form_hmaps(raw_masks, num_rois, rois, hmap_size, num_classes):
         gen_bt_masks.append(ops.bilinear_resize(re_raw_masks, hmap_size[i], hmap_size[i]))
     gen_fm_bt_masks = ops.bilinear_resize(re_raw_masks, hmap_size[0] // 2, hmap_size[0] // 2)
     return gen_hmaps, gen_bt_masks, gen_fm_bt_masks
+
+
+# ---- FID (reference utils.py:358-362, 586-714) ---------------------------------------------------
+def denorm_imgs(images):
+    """[-1, 1] float images -> uint8 [0, 255] numpy array (reference utils.py:358-362)."""
+    return images.add(1).div(2).mul(255).clamp(0, 255).byte().detach().cpu().numpy()
+
+
+@torch.no_grad()
+def get_activations(images, model, batch_size, verbose=False):
+    """pool3 activations [n_used, cfg.TEST.FID_DIMS] of `images` ([-1, 1], [n, 3, h, w]) through the FID network, in
+    whole batches only: the n % batch_size trailing images are dropped, like the reference (utils.py:587-641).  The
+    result stays on the device as fp32 (the reference copies every batch to a host float64 array): the statistics
+    are accumulated there (objgan_hip.ops.MomentAccumulator)."""
+    model.eval()
+    total = int(images.size(0))
+    step = min(int(batch_size), total)
+    if step < batch_size:
+        print('get_activations: only %d images for batch size %d, running one batch of %d' % (total, batch_size, step))
+    whole = total // step if step else 0
+    feats = []
+    for k, chunk in enumerate(images[:whole * step].split(step) if whole else ()):
+        pooled = model(chunk)[0]
+        if tuple(pooled.shape[2:]) != (1, 1):
+            raise ValueError("get_activations: expected pooled [B, D, 1, 1] features, got %s" % (tuple(pooled.shape),))
+        feats.append(pooled.flatten(1).clone())     # a graphed model returns shared storage: keep a copy
+        if verbose:
+            print('get_activations: batch %d of %d' % (k + 1, whole), flush=True)
+    return torch.cat(feats, 0) if feats else images.new_zeros((0, cfg.TEST.FID_DIMS))
+
+
+def calculate_activation_statistics(act):
+    """(mean, covariance) of host activations [n, dim] (reference utils.py:644-657); kept for callers that hold the
+    activations on the host -- the evaluator accumulates the same statistics on the device."""
+    return np.mean(act, axis=0), np.cov(act, rowvar=False)
+
+
+def _sqrt_of_product(c1, c2, eps):
+    """scipy's sqrtm(c1 c2); a non-finite result (singular product) is retried with `eps` on both diagonals."""
+    from scipy import linalg
+    root, _ = linalg.sqrtm(c1.dot(c2), disp=False)
+    if np.isfinite(root).all():
+        return root
+    print('calculate_frechet_distance: sqrtm(sigma1 sigma2) is not finite, retrying with %g on both diagonals' % eps)
+    ridge = np.eye(c1.shape[0]) * eps
+    return linalg.sqrtm((c1 + ridge).dot(c2 + ridge))
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """d^2 = |mu1 - mu2|^2 + Tr(C1 + C2 - 2 sqrt(C1 C2)) between two Gaussians, on the host in fp64 (reference
+    utils.py:660-714: scipy's sqrtm, `eps` on both diagonals when the product is singular, a ValueError for a
+    square root whose diagonal has an imaginary part above 1e-3).  One 2048 x 2048 sqrtm per evaluation."""
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape:
+        raise ValueError("calculate_frechet_distance: statistics of different sizes: means %s / %s, covariances %s / %s"
+                         % (mu1.shape, mu2.shape, sigma1.shape, sigma2.shape))
+    root = _sqrt_of_product(sigma1, sigma2, eps)
+    if np.iscomplexobj(root):       # rounding leaves a small imaginary part; a large one means a bad covariance
+        if not np.all(np.abs(np.diagonal(root).imag) <= 1e-3):
+            raise ValueError("calculate_frechet_distance: sqrtm(sigma1 sigma2) is complex, largest imaginary part %g"
+                             % np.max(np.abs(root.imag)))
+        root = root.real
+    gap = mu1 - mu2
+    return gap.dot(gap) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(root)

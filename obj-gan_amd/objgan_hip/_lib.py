@@ -58,6 +58,9 @@ SIGNATURES = {
     "objgan_softmax_strided_backward": [_ptr, _ptr, _ptr, _c_long, _c_int, _c_long, _c_float, _ptr],
     "objgan_bilinear_forward": [_ptr, _ptr, _c_long, _c_int, _c_int, _c_int, _c_int, _ptr],
     "objgan_bilinear_backward": [_ptr, _ptr, _c_long, _c_int, _c_int, _c_int, _c_int, _ptr],
+    "objgan_bilinear_halfpixel_forward": [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr],
+    "objgan_moments_accumulate": [_ptr, _c_int, _c_int, _ptr, _ptr, _ptr],
+    "objgan_moments_finalize": [_ptr, _ptr, _c_long, _c_int, _ptr, _ptr, _ptr],
     "objgan_sum2x2": [_ptr, _ptr, _c_long, _c_int, _c_int, _ptr],
     "objgan_reflect_fold": [_ptr, _ptr, _c_long, _c_int, _c_int, _ptr],
     "objgan_conv_pack_job_bytes": [],

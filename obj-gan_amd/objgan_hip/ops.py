@@ -1642,6 +1642,63 @@ def bilinear_resize(x, oh, ow):
     return _BilinearFn.apply(x, int(oh), int(ow))
 
 
+def bilinear_resize_halfpixel(x, oh, ow, scale=None, shift=None):
+    """F.interpolate(x, size=(oh, ow), mode='bilinear', align_corners=False) of an [N, C, H, W] tensor, then
+    y * scale[c] + shift[c] when the two per-channel tables are given.  Forward only: the input preparation of the
+    frozen FID feature network (csrc/eval_stats.hip)."""
+    _chk(x, scale, shift)
+    if x.dim() != 4:
+        raise _lib.ObjganHipError("bilinear_resize_halfpixel: expects [N, C, H, W]")
+    if (scale is None) != (shift is None):
+        raise _lib.ObjganHipError("bilinear_resize_halfpixel: scale and shift go together")
+    x = _c(x.detach())
+    N, C, H, W = x.shape
+    if scale is not None:
+        scale, shift = _c(scale.detach()).reshape(-1), _c(shift.detach()).reshape(-1)
+        if scale.numel() != C or shift.numel() != C:
+            raise _lib.ObjganHipError("bilinear_resize_halfpixel: scale / shift need one value per channel")
+    y = torch.empty((N, C, int(oh), int(ow)), dtype=_F32, device=x.device)
+    _lib.call("objgan_bilinear_halfpixel_forward", _p(x), _p(y), N, C, H, W, int(oh), int(ow), _p(scale), _p(shift),
+              _stream())
+    return y
+
+
+class MomentAccumulator(object):
+    """Streaming mean / covariance of fp32 rows in fp64 on the device (csrc/eval_stats.hip): `add(x)` takes [rows, D]
+    blocks, `finalize()` returns (mu [D], sigma [D, D]) as fp64 tensors -- np.mean(axis=0) / np.cov(rowvar=False) of all
+    rows added so far.  One thread owns each accumulator element and adds rows in order, so the statistics are
+    bit-reproducible and do not depend on how the rows were cut into `add` calls.  A call streams the D x D
+    accumulator once (32 MB at D = 2048): callers with small batches stage a few of them per call."""
+
+    def __init__(self, D, device):
+        self.D = int(D)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.ObjganHipError("MomentAccumulator: needs a HIP device (no CPU path)")
+        self.sum = torch.zeros(self.D, dtype=torch.float64, device=self.device)
+        self.outer = torch.zeros(self.D, self.D, dtype=torch.float64, device=self.device)   # upper triangle
+        self.count = 0
+
+    def add(self, x):
+        _chk(x)
+        if x.dim() != 2 or x.shape[1] != self.D:
+            raise _lib.ObjganHipError("MomentAccumulator.add: expects [rows, %d]" % self.D)
+        x = _c(x.detach())
+        rows = int(x.shape[0])
+        if rows:
+            _lib.call("objgan_moments_accumulate", _p(x), rows, self.D, _p(self.sum), _p(self.outer), _stream())
+            self.count += rows
+
+    def finalize(self):
+        if self.count < 2:
+            raise _lib.ObjganHipError("MomentAccumulator.finalize: a covariance needs at least two rows")
+        mu = torch.empty(self.D, dtype=torch.float64, device=self.device)
+        sigma = torch.empty(self.D, self.D, dtype=torch.float64, device=self.device)
+        _lib.call("objgan_moments_finalize", _p(self.sum), _p(self.outer), self.count, self.D, _p(mu), _p(sigma),
+                  _stream())
+        return mu, sigma
+
+
 # ---- training images: baseline JPEG decode on the device (csrc/jpeg.hip) ---------------------------------
 class JpegUnsupported(_lib.ObjganHipError):
     """the file is not a baseline / sequential Huffman JPEG in a supported sampling (progressive, arithmetic, CMYK ...):
