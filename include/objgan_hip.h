@@ -394,6 +394,31 @@ int objgan_moments_accumulate(const float* x, int rows, int D, double* sum, doub
 int objgan_moments_finalize(const double* sum, const double* outer, long n, int D, double* mu, double* sigma,
                             void* stream);
 
+/* ---- caption / attention snapshot grids on the device (csrc/snapshot.hip) ---------------------------------
+ * The grid of reference image_generation/miscc/utils.py:59-182 (build_super_images; per_panel_norm = 1: :184-306,
+ * build_super_shape_images) for the first nvis images of a batch: per image font_max rows of caption strip, one line
+ * [lr image | 2-px pad | panel 0 | pad | ... | panel max_word_num | pad] and one line [image | pad | merged 0 | ...].
+ * imgs [>= nvis, 3, H, W] and lr_imgs [>= nvis, 3, LH, LW] (NULL: the image itself) in [-1, 1], resized to vis x vis with
+ * half-pixel bilinear sampling, (x + 1) / 2 * 255 in three fp32 roundings, truncated.  attn [>= nvis, T, a, a], T <= 1023:
+ * panel 0 is the maximum over the T maps, panels 1..T the maps, panels past T zeros; only the first max_word_num + 1 are
+ * drawn, all take part in the image's minimum / maximum.  counts (device, nvis ints, may be NULL): image n has only
+ * counts[n] <= T maps (the per-caption maps of the DAMSM word loss), the slots behind them are ignored.  M (device, fp64 [vis, a]; needs vis / a >= 2): a map expands
+ * to M A M^T in fp64 -- skimage's pyramid_expand(sigma = 20) as scipy.ndimage evaluates it, see csrc/snapshot.hip; M NULL
+ * (needs vis == a): the maps are drawn as they are and normalised in fp32, the reference's dtype on that path.  Normalisation
+ * (v - min) / (max - min) * 255, truncated: min(1, .) / max(0, .) over all panels of the image, or per panel and skipped
+ * where max == min (per_panel_norm).  max == min in the global form (the reference's 0 / 0, an undefined cast): the panel
+ * is 0.  Merged panels: Pillow's paste(att, mask = L 210) over the image byte; objgan_snapshot_blend_table (HOST ONLY)
+ * writes that blend for all 256 x 256 (image byte, attention byte) pairs.  strip: uint8 [nvis * font_max, Wg, 3],
+ * out: uint8 [nvis * (font_max + 2 vis), Wg, 3], Wg = (max_word_num + 2) * (vis + 2); every byte of out is written.
+ * ws: objgan_snapshot_ws_doubles doubles (HOST ONLY query; 0 = arguments out of range).  Statistics are combined in a
+ * fixed order without atomics: the grid is bit-reproducible. */
+long objgan_snapshot_ws_doubles(int nvis, int T, int a, int vis);
+int objgan_snapshot_blend_table(unsigned char* table65536);
+int objgan_snapshot_grid(const float* imgs, const float* lr_imgs, const float* attn, const int* counts, const double* M,
+                         const unsigned char* strip, unsigned char* out, double* ws, long ws_doubles,
+                         int nvis, int T, int a, int vis, int H, int W, int LH, int LW,
+                         int max_word_num, int font_max, int per_panel_norm, void* stream);
+
 /* ---- measurement aid (bench.py roofline leg): hipEvent-bracketed conv launches ------------------ */
 int objgan_prof_enable(int on);
 int objgan_prof_collect(double* ms, double* flops, long* count);   /* arrays of 192 categories (48..95: fp16x2 instances; 96..191: fp16x2 on records, one / two pixel groups) */

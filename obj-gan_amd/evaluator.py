@@ -12,8 +12,10 @@ largest box count (one scalar, one sync), and the real images' activations arriv
 uploaded ([B, 2048] fp64).  The Frechet distance itself (one 2048 x 2048 matrix square root per evaluation) is scipy's,
 on the host.
 
-Not here: TensorFlow Inception (cfg.TEST.USE_TF is answered with a notice and the PyTorch route), the caption /
-attention snapshot grids (cfg.TEST.SAVE_OPTIONS == 'SNAPSHOT' saves single images instead), building the
+cfg.TEST.SAVE_OPTIONS == 'SNAPSHOT' also writes the caption / attention grids of every displayed batch into
+`<output>/Snapshot/` (composed on the device, miscc.utils.build_super_images; one uint8 array per grid comes back).
+
+Not here: TensorFlow Inception (cfg.TEST.USE_TF is answered with a notice and the PyTorch route), building the
 `*_insanns.pickle` files from COCO JSON, more than one GPU.
 """
 import os
@@ -124,6 +126,7 @@ class condGANEvaluator(object):
     def __init__(self, output_dir, data_loader, dataset, device=None):
         self.image_dir = os.path.join(output_dir, 'Image') if output_dir else ''
         self.score_dir = os.path.join(output_dir, 'Score') if output_dir else ''
+        self.snapshot_dir = os.path.join(output_dir, 'Snapshot') if output_dir else ''      # made when first written to
         for d in (self.image_dir, self.score_dir):
             if d:
                 mkdir_p(d)
@@ -267,6 +270,44 @@ class condGANEvaluator(object):
             out["is_pred"] = self.inception_model(fake_imgs[-1])
         return out
 
+    def save_img_results(self, fake_imgs, attn_maps, bt_attn_maps, captions, cap_lens, gen_iterations):
+        """Snapshot/G_<n>_<i>.png and bt_G_<n>_<i>.png per attention stage (reference evaluator.py:170-205).  The
+        reference's own call hands build_super_images keyword arguments it does not take (font_max, font_size) and
+        raises; this is the trainer's form of the call (reference trainer.py:284-312).  -> the paths written."""
+        from PIL import Image
+        from miscc.utils import build_super_images
+        mkdir_p(self.snapshot_dir)
+        written = []
+        for i in range(len(attn_maps)):
+            img, lr_img = (fake_imgs[i + 1], fake_imgs[i]) if len(fake_imgs) > 1 else (fake_imgs[0], None)
+            for prefix, maps in (("G", attn_maps[i]), ("bt_G", bt_attn_maps[i])):
+                img_set, _ = build_super_images(img.detach(), captions, self.ixtoword, maps, int(maps.size(2)),
+                                                lr_imgs=None if lr_img is None else lr_img.detach())
+                path = '%s/%s_%d_%d.png' % (self.snapshot_dir, prefix, gen_iterations, i)
+                Image.fromarray(img_set).save(path)
+                written.append(path)
+        return written
+
+    def save_shape_results(self, imgs, hmaps, rois, num_rois, gen_iterations, model_type):
+        """Snapshot/Shape<G|D>_<n>.png (reference evaluator.py:207-229): the real 64 x 64 images beside the per-box
+        masks (G: generated) or the per-class layout maps (D: ground truth), every panel normalised on its own; the
+        caption row of an image lists the first word of each box's category name."""
+        from PIL import Image
+        from miscc.utils import build_super_shape_images
+        mkdir_p(self.snapshot_dir)
+        B = int(hmaps.size(0))
+        rois_np, nr = _host(rois), _host(num_rois).tolist()
+        captions = torch.zeros(B, cfg.ROI.BOXES_NUM)
+        for b in range(B):
+            for r in range(int(nr[b])):
+                captions[b, r] = self.cats_dict[int(rois_np[b, r, 4])][0]
+        img_set, _ = build_super_shape_images(imgs.detach(), captions, self.ixtoword, hmaps.detach(), int(hmaps.size(2)),
+                                              lr_imgs=None, font_max=20, font_size=12, max_word_num=cfg.ROI.BOXES_NUM,
+                                              batch_size=B)
+        path = '%s/Shape%s_%d.png' % (self.snapshot_dir, model_type, gen_iterations)
+        Image.fromarray(img_set).save(path)
+        return path
+
     def save_singleimages(self, images, keys, sent_ids):
         """evaluator.py:225-233: [-1, 1] images -> <Image>/<key>_<sent id>.jpg"""
         from PIL import Image
@@ -327,8 +368,7 @@ class condGANEvaluator(object):
             raise RuntimeError("R-precision needs the DAMSM image encoder: %s is missing"
                                % cfg.TRAIN.NET_E.replace('text_encoder', 'image_encoder'))
         clabels_emb = self.prepare_cat_emb()
-        if cfg.TEST.SAVE_OPTIONS == 'SNAPSHOT':
-            print("cfg.TEST.SAVE_OPTIONS == 'SNAPSHOT': caption / attention grids are not drawn here; saving single images")
+        snapshots = bool(self.snapshot_dir) and cfg.TEST.SAVE_OPTIONS == 'SNAPSHOT'
         save_images = bool(self.image_dir) and cfg.TEST.SAVE_OPTIONS in ('IMAGE', 'SNAPSHOT')
         pool = RPrecisionPool(cfg.TEST.RP_POOL_SIZE, self.prepare_labels())
         fake_stats = StagedMoments(cfg.TEST.FID_DIMS, self.device)
@@ -365,6 +405,13 @@ class condGANEvaluator(object):
             if gen_iterations % self.display_interval == 0:
                 if save_images:
                     self.save_singleimages(images, keys, sent_ids)
+                if snapshots:
+                    self.save_img_results(out["fake_imgs"], out["attn_maps"], out["bt_attn_maps"], captions, cap_lens,
+                                          gen_iterations)
+                    if cfg.TEST.USE_GT_BOX_SEG > 0:
+                        self.save_shape_results(imgs[0], out["raw_masks"], rois[0], num_rois, gen_iterations, 'G')
+                        if gt_hmaps is not None:
+                            self.save_shape_results(imgs[0], gt_hmaps[0].squeeze(), rois[0], num_rois, gen_iterations, 'D')
                 print('%d / %d' % (gen_iterations, self.num_batches))
             # (5) intermediate results
             region_features, cnn_code = image_encoder(images)

@@ -1,7 +1,8 @@
 """Hot-path helpers of the image generator (the subset of reference
 image_generation/miscc/utils.py that the G+D training step calls: :309-329, :365-413,
-:445-522) and its Inception-score / FID utilities (:358-362, :417-441, :586-714).  The visualisation
-utilities of the reference file (image grids) are not provided.
+:445-522), its Inception-score / FID utilities (:358-362, :417-441, :586-714) and its caption / attention
+snapshot grids (:22-306): the caption strip is drawn on the host with PIL, everything below it is composed on
+the device (objgan_hip.ops.snapshot_grid) and only the finished uint8 grid is copied back.
 """
 import random
 from copy import deepcopy
@@ -12,6 +13,106 @@ import torch.nn as nn
 
 from miscc.config import cfg
 from objgan_hip import ops
+
+
+# ---- caption / attention snapshot grids (reference utils.py:22-306) ---------------------------------
+COLOR_DIC = {0: [128, 64, 128], 1: [244, 35, 232], 2: [70, 70, 70], 3: [102, 102, 156], 4: [190, 153, 153],
+             5: [153, 153, 153], 6: [250, 170, 30], 7: [220, 220, 0], 8: [107, 142, 35], 9: [152, 251, 152],
+             10: [70, 130, 180], 11: [220, 20, 60], 12: [255, 0, 0], 13: [0, 0, 142], 14: [119, 11, 32],
+             15: [0, 60, 100], 16: [0, 80, 100], 17: [0, 0, 230], 18: [0, 0, 70], 19: [0, 0, 0]}
+FONT_MAX = 50
+_FONTS = {}
+_FONT_FALLBACKS = ("FreeMono.ttf", "DejaVuSansMono.ttf", "LiberationMono-Regular.ttf", "DejaVuSans.ttf", "Arial.ttf")
+
+
+def caption_font(size=50):
+    """The reference's font, cfg.DATA_DIR + '/share/Pillow/Tests/fonts/FreeMono.ttf' (utils.py:41).  Without that
+    file: any TrueType font Pillow finds on this machine, then Pillow's built-in one -- one notice per process, never
+    an exception (a missing font must not end a training run)."""
+    from PIL import ImageFont
+    path = str(getattr(cfg, "DATA_DIR", "")) + '/share/Pillow/Tests/fonts/FreeMono.ttf'
+    key = (path, size)
+    if key in _FONTS:
+        return _FONTS[key]
+    fnt, used = None, None
+    for cand in (path,) + _FONT_FALLBACKS:
+        try:
+            fnt, used = ImageFont.truetype(cand, size), cand
+            break
+        except Exception:
+            continue
+    if fnt is None:
+        try:
+            fnt, used = ImageFont.load_default(), "Pillow's built-in font"
+        except Exception:
+            used = "no font: captions are not drawn"
+    if used != path and not _FONTS.get("noticed"):
+        _FONTS["noticed"] = True
+        print("snapshot grids: caption font %s not found, using %s" % (path, used))
+    _FONTS[key] = fnt
+    return fnt
+
+
+def drawCaption(convas, captions, ixtoword, vis_size, off1=2, off2=2):
+    """Draw '%d:%s' % (j, word[:6]) labels of every caption onto the uint8 canvas, caption i at row i * FONT_MAX, word
+    j at column (j + off1) * (vis_size + off2) (reference utils.py:36-56; text past the canvas is clipped).
+    -> (PIL image, list of word lists)."""
+    from PIL import Image, ImageDraw
+    img_txt = Image.fromarray(convas)
+    fnt = caption_font(50)
+    d = ImageDraw.Draw(img_txt)
+    caps = _host(captions)
+    sentence_list = []
+    for i in range(caps.shape[0]):
+        sentence = []
+        for j in range(caps.shape[1]):
+            if caps[i, j] == 0:
+                break
+            word = ixtoword[int(caps[i, j])].encode('ascii', 'ignore').decode('ascii')
+            if fnt is not None and i * FONT_MAX < convas.shape[0]:
+                d.text(((j + off1) * (vis_size + off2), i * FONT_MAX), '%d:%s' % (j, word[:6]), font=fnt,
+                       fill=(255, 255, 255, 255))
+            sentence.append(word)
+        sentence_list.append(sentence)
+    return img_txt, sentence_list
+
+
+def _super_images(real_imgs, captions, ixtoword, attn_maps, att_sze, lr_imgs, font_max, max_word_num, nvis, off1, off2,
+                  per_panel_norm):
+    vis_size = att_sze * 16 if att_sze == 17 else int(real_imgs.size(2))
+    text_convas = np.ones([nvis * font_max, (max_word_num + 2) * (vis_size + 2), 3], dtype=np.uint8)
+    for i in range(max_word_num):
+        text_convas[:, (i + 2) * (vis_size + 2):(i + 3) * (vis_size + 2), :] = COLOR_DIC[i]
+    text_map, sentences = drawCaption(text_convas, captions, ixtoword, vis_size, off1, off2)
+    strip = h2d(np.array(text_map, dtype=np.uint8), real_imgs.device)
+    grid = ops.snapshot_grid(real_imgs, attn_maps, att_sze, strip, lr_imgs=lr_imgs, max_word_num=max_word_num,
+                             font_max=font_max, nvis=nvis, per_panel_norm=per_panel_norm)
+    return grid.cpu().numpy(), sentences          # the one device-to-host copy: the finished grid
+
+
+def build_super_images(real_imgs, captions, ixtoword, attn_maps, att_sze, lr_imgs=None, batch_size=None,
+                       max_word_num=None):
+    """Reference utils.py:59-182 for DEVICE tensors: per image a caption strip, [lr image | attention panels] and
+    [image | panels pasted over the image]; minimum / maximum over all panels of an image.  attn_maps: [B, T, a, a] or
+    a list of per-image [1, T_i, a, a].  -> (uint8 ndarray, sentences).  batch_size / max_word_num default to
+    cfg.TRAIN.BATCH_SIZE / cfg.TEXT.WORDS_NUM at call time.  Deviation: nvis = min(8, B) -- the reference indexes past a
+    batch of fewer than 8; from B = 8 on the grid is the reference's."""
+    max_word_num = cfg.TEXT.WORDS_NUM if max_word_num is None else max_word_num
+    nvis = min(8, int(real_imgs.size(0)))
+    return _super_images(real_imgs, captions, ixtoword, attn_maps, att_sze, lr_imgs, FONT_MAX, max_word_num, nvis, 2, 2,
+                         False)
+
+
+def build_super_shape_images(real_imgs, captions, ixtoword, attn_maps, att_sze, lr_imgs=None, font_max=50,
+                             font_size=50, batch_size=None, max_word_num=None):
+    """Reference utils.py:184-306: the same grid with every panel normalised by its own minimum / maximum (a constant
+    panel is drawn as it is) and strips of `font_max` rows.  As in the reference, font_max / font_size reach
+    drawCaption as its column offsets off1 / off2, so labels land at column (j + font_max) * (vis_size + font_size)."""
+    max_word_num = cfg.TEXT.WORDS_NUM if max_word_num is None else max_word_num
+    batch_size = int(real_imgs.size(0)) if batch_size is None else batch_size
+    nvis = min(8, batch_size, int(real_imgs.size(0)))
+    return _super_images(real_imgs, captions, ixtoword, attn_maps, att_sze, lr_imgs, font_max, max_word_num, nvis,
+                         font_max, font_size, True)
 
 
 # ---- host copies of the small box tensors ---------------------------------------------------------

@@ -24,7 +24,9 @@ if os.environ.get("OBJGAN_DEV") == "1":
 # -munsafe-fp-atomics (hardware fp32 atomic add instead of a CAS loop) only where a float atomic is left: the
 # reference-signature objgan_roi_align_backward (unordered scatter, as the CUDA original).  The convolution files carry
 # no fp32 atomic any more (round 5: the first-generation split-K path is gone); the training step runs without any.
-PER_FILE_FLAGS = {"roi_align.hip": ["-ffp-contract=off", "-munsafe-fp-atomics"], "resize_pil.hip": ["-ffp-contract=off"]}
+# The snapshot grids round (x + 1) / 2 * 255 and (v - min) / (max - min) * 255 operation by operation, like numpy.
+PER_FILE_FLAGS = {"roi_align.hip": ["-ffp-contract=off", "-munsafe-fp-atomics"], "resize_pil.hip": ["-ffp-contract=off"],
+                  "snapshot.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -1957,6 +1957,116 @@ def resize_masks(masks, sizes):
     return outs
 
 
+# ---- caption / attention snapshot grids (csrc/snapshot.hip) ---------------------------------------------
+_EXPAND = {}
+
+
+def expansion_matrix(a, vis, sigma=20.0):
+    """fp64 [vis, a]: `skimage.transform.pyramid_expand(x, upscale=vis // a, sigma=sigma)` along one axis, as
+    scipy.ndimage evaluates it -- order-1 zoom (grid_mode, mode 'mirror') to vis samples, then the truncate-4 Gaussian
+    with mode 'mirror'; the radius (80 at sigma 20) exceeds a small panel several times over, so the mirror image is
+    taken with its period 2 vis - 2.  Both steps are linear: a 2-D map A expands to M A M^T."""
+    import numpy as np
+    a, vis = int(a), int(vis)
+
+    def mirror(i, n):
+        if n == 1:
+            return 0
+        i = i % (2 * n - 2)
+        return i if i < n else 2 * n - 2 - i
+
+    Z = np.zeros((vis, a), np.float64)
+    for o in range(vis):
+        c = (o + 0.5) * (a / float(vis)) - 0.5
+        if a == 1:
+            c = 0.0
+        elif c < 0:
+            c = -c                      # (|c| <= 0.5: one reflection about sample 0)
+        # (past the last sample, c < a: scipy keeps the coordinate and mirrors the upper neighbour's index)
+        i = int(np.floor(c))
+        f = c - i
+        Z[o, mirror(i, a)] += 1.0 - f
+        Z[o, mirror(i + 1, a)] += f
+    w = _gaussian_taps(sigma)
+    r = len(w) // 2
+    G = np.zeros((vis, vis), np.float64)
+    for o in range(vis):
+        for k in range(-r, r + 1):
+            G[o, mirror(o + k, vis)] += w[k + r]
+    return G.dot(Z)
+
+
+def _expansion_matrix_dev(a, vis, device):
+    key = (int(a), int(vis), str(device))
+    m = _EXPAND.get(key)
+    if m is None:
+        # staged through pinned memory: the upload is a stream operation, not a host-device synchronisation
+        m = _EXPAND[key] = torch.from_numpy(expansion_matrix(a, vis)).pin_memory().to(device, non_blocking=True)
+    return m
+
+
+def paste_blend_table():
+    """uint8 numpy [256, 256]: byte of a merged panel for (image byte, attention byte) -- Pillow's
+    paste(att, (0, 0), mask = L 210) as the compose kernel evaluates it (host only)."""
+    import numpy as np
+    table = np.empty((256, 256), np.uint8)
+    _lib.call("objgan_snapshot_blend_table", ctypes.c_void_p(table.ctypes.data))
+    return table
+
+
+def snapshot_grid(imgs, attn_maps, att_sze, text_strip, lr_imgs=None, max_word_num=12, font_max=50, nvis=8,
+                  per_panel_norm=False):
+    """The caption / attention grid of reference miscc/utils.py:59-182 (per_panel_norm: :184-306) for the first `nvis`
+    images, composed on the device: uint8 [nvis * (font_max + 2 vis), (max_word_num + 2) * (vis + 2), 3] with
+    vis = 272 when att_sze == 17 and the image size otherwise.  imgs / lr_imgs [B, 3, h, w] in [-1, 1]; attn_maps
+    [B, T, att_sze, att_sze] (any shape that views as that), or a list of per-image [1, T_i, att_sze, att_sze] tensors (the
+    per-caption maps of the DAMSM word loss); text_strip: uint8 device tensor [nvis * font_max, width, 3], the caption
+    rows drawn by the caller.  No device->host synchronisation."""
+    as_list = isinstance(attn_maps, (list, tuple))
+    _chk(imgs, lr_imgs, *(attn_maps if as_list else (attn_maps,)))
+    if not (torch.is_tensor(text_strip) and text_strip.is_cuda and text_strip.dtype == torch.uint8):
+        raise _lib.ObjganHipError("snapshot_grid: text_strip is a uint8 tensor on the GPU (there is no CPU path)")
+    if imgs.dim() != 4 or imgs.shape[1] != 3 or (lr_imgs is not None and (lr_imgs.dim() != 4 or lr_imgs.shape[1] != 3)):
+        raise _lib.ObjganHipError("snapshot_grid: images are [B, 3, h, w]")
+    B, a, nvis, font_max, mw = int(imgs.shape[0]), int(att_sze), int(nvis), int(font_max), int(max_word_num)
+    H, W = int(imgs.shape[2]), int(imgs.shape[3])
+    vis = a * 16 if a == 17 else H
+    if (not 1 <= nvis <= B or (len(attn_maps) if as_list else attn_maps.shape[0]) < nvis
+            or (lr_imgs is not None and lr_imgs.shape[0] < nvis)):
+        raise _lib.ObjganHipError("snapshot_grid: nvis = %d images wanted, batch of %d" % (nvis, B))
+    counts = None
+    if as_list:
+        # the shapes are host knowledge: one zero-padded table and one small upload through pinned memory
+        per = [m.detach().reshape(-1, a, a) for m in attn_maps[:nvis]]
+        sizes = [int(m.shape[0]) for m in per]
+        attn = torch.zeros((nvis, max(sizes + [1]), a, a), dtype=_F32, device=imgs.device)
+        for i, m in enumerate(per):
+            attn[i, :sizes[i]].copy_(m)
+        if min(sizes) < 1:
+            raise _lib.ObjganHipError("snapshot_grid: an image without attention maps")
+        counts = torch.tensor(sizes, dtype=torch.int32).pin_memory().to(imgs.device, non_blocking=True)
+    else:
+        attn = _c(attn_maps.detach()).reshape(int(attn_maps.shape[0]), -1, a, a)
+    T = int(attn.shape[1])
+    ratio = vis // a
+    if ratio < 1 or (ratio == 1 and vis != a) or not 1 <= T <= 1023:
+        raise _lib.ObjganHipError("snapshot_grid: %d maps of %d x %d cannot be drawn into %d x %d panels" % (T, a, a, vis, vis))
+    width = (mw + 2) * (vis + 2)
+    if tuple(text_strip.shape) != (nvis * font_max, width, 3):
+        raise _lib.ObjganHipError("snapshot_grid: text_strip is %s, expected %s"
+                                  % (tuple(text_strip.shape), (nvis * font_max, width, 3)))
+    imgs = _c(imgs.detach())
+    lr = _c(lr_imgs.detach()) if lr_imgs is not None else None
+    LH, LW = (int(lr.shape[2]), int(lr.shape[3])) if lr is not None else (0, 0)
+    M = _expansion_matrix_dev(a, vis, imgs.device) if ratio > 1 else None
+    nws = _q("objgan_snapshot_ws_doubles", nvis, T, a, vis)
+    ws = torch.empty(nws, dtype=torch.float64, device=imgs.device)
+    out = torch.empty((nvis * (font_max + 2 * vis), width, 3), dtype=torch.uint8, device=imgs.device)
+    _lib.call("objgan_snapshot_grid", _p(imgs), _p(lr), _p(attn), _p(counts), _p(M), _p(_c(text_strip)), _p(out), _p(ws), nws,
+              nvis, T, a, vis, H, W, LH, LW, mw, font_max, 1 if per_panel_norm else 0, _stream())
+    return out
+
+
 # ---- layout-map stem of the object discriminators, evaluated below the 512x512 lift -------------------
 # conv3x3(reflect_pad(lift(seg)))[co] = sum_taps (shift_tap o reflect o lift)(conv1x1(seg; W[:, :, tap])[co]):
 # the channel contraction is a 1x1 convolution at the source resolution (MFMA kernel), the pixel operators

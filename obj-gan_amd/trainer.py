@@ -303,6 +303,7 @@ class condGANTrainer(object):
         self.max_epoch = cfg.TRAIN.MAX_EPOCH
         self.snapshot_interval = cfg.TRAIN.SNAPSHOT_INTERVAL
         self.print_interval = cfg.TRAIN.PRINT_INTERVAL
+        self.display_interval = cfg.TRAIN.DISPLAY_INTERVAL
         self.data_loader = data_loader
         self.dataset = dataset
         self.num_batches = len(data_loader) if data_loader is not None else 0
@@ -442,6 +443,11 @@ class condGANTrainer(object):
         self.clabels_emb = self.prepare_cat_emb() if self.cat_labels is not None else None
         self.match_labels = self.prepare_labels()
         self.noise = torch.empty(self.batch_size, cfg.GAN.Z_DIM, device=self.device)
+        # the noise of every snapshot grid (reference trainer.py:342-344), drawn once from a generator of its own: the
+        # global stream, and with it the noise of the training steps, is what it was without the snapshots
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(torch.initial_seed() + 1)
+        self.fixed_noise = torch.randn(self.batch_size, cfg.GAN.Z_DIM, device=self.device, generator=gen)
         self.gen_iterations = 0
         return self
 
@@ -875,6 +881,58 @@ class condGANTrainer(object):
                 arena.epoch[0] += 1
         return fake_imgs, att, bt_att
 
+    # ---- snapshot grids (reference trainer.py:275-330) ------------------------------------------------
+    @torch.no_grad()
+    def save_img_results(self, batch, noise, gen_iterations, name='current'):
+        """Caption / attention grids of one batch into Image/: per attention stage i `G_<name>_<n>_<i>.png` (word
+        attention) and `bt_G_<name>_<n>_<i>.png` (bottom-up attention) over the stage's output, and `D_<name>_<n>.png`, the
+        DAMSM word attention of the frozen image encoder on the last fake image.  The generator runs in eval mode with
+        the EMA weights (`sample`); the grids are composed on the device (miscc.utils.build_super_images) and each
+        leaves it as one uint8 array.  Nothing the training step reads is changed.  -> the paths written."""
+        from PIL import Image
+        from miscc.utils import build_super_images
+        from miscc.losses import words_loss
+        b = batch
+        B = int(b["num_rois"].shape[0])
+        if self.text_encoder is not None and "captions" in b:
+            captions, cap_lens = b["captions"], b["cap_lens"]
+            words_embs, sent_emb = self.text_encoder(captions, cap_lens, int(b.get("max_len", captions.shape[1])))
+            words_embs, sent_emb = words_embs.detach().clone(), sent_emb.detach().clone()
+            num_words = words_embs.size(2)
+            mask, glove_words_embs = (captions == 0)[:, :num_words], b.get("glove_words_embs")
+            if self.glove_emb is not None and "glove_captions" in b:
+                gc = b["glove_captions"]
+                gw = torch.nn.functional.embedding(gc.reshape(-1), self.glove_emb.weight)
+                glove_words_embs = gw.view(gc.size(0), gc.size(1), -1)[:, :num_words].transpose(1, 2)
+        else:
+            words_embs, sent_emb = b["words_embs"], b["sent_emb"]
+            mask, glove_words_embs = b.get("mask"), b.get("glove_words_embs")
+        captions = b["captions"] if "captions" in b else torch.zeros(B, 1, dtype=torch.long)
+        ixtoword = self.ixtoword if self.ixtoword is not None else {}
+        # the conditioning augmentation draws its eps from the global stream (model.py CA_NET): drawn under a forked
+        # generator state, so that a run with snapshots trains on the same random numbers as one without
+        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
+            fake_imgs, attention_maps, bt_attention_maps = self.sample(b, noise[:B], words_embs, sent_emb,
+                                                                       glove_words_embs, mask, use_ema=True)
+        written = []
+
+        def save(img_set, path):
+            Image.fromarray(img_set).save(path)
+            written.append(path)
+
+        for i in range(len(attention_maps)):
+            img, lr_img = (fake_imgs[i + 1], fake_imgs[i]) if len(fake_imgs) > 1 else (fake_imgs[0], None)
+            for prefix, maps in (("G", attention_maps[i]), ("bt_G", bt_attention_maps[i])):
+                img_set, _ = build_super_images(img, captions, ixtoword, maps, int(maps.size(2)), lr_imgs=lr_img)
+                save(img_set, '%s/%s_%s_%d_%d.png' % (self.image_dir, prefix, name, gen_iterations, i))
+        if self.image_encoder is not None and "cap_lens" in b:
+            # (the graphed encoder hands out its static output buffer on the no-grad path: keep a copy)
+            region_features = self._graphed("image_encoder")(fake_imgs[-1])[0].detach().clone()
+            _, _, att_maps, _ = words_loss(region_features, words_embs.detach(), None, b["cap_lens"], None, B)
+            img_set, _ = build_super_images(fake_imgs[-1], captions, ixtoword, att_maps, int(region_features.size(2)))
+            save(img_set, '%s/D_%s_%d.png' % (self.image_dir, name, gen_iterations))
+        return written
+
     # ---- checkpoints (reference trainer.py:251-273) ---------------------------------------------------
     def save_model(self, netG, avg_param_G, netsPatD, netsShpD, netObjSSD, netObjLSD, epoch):
         if self.rank != 0:
@@ -931,6 +989,11 @@ class condGANTrainer(object):
                 out = self.train_step(batch, want_logs=log_now)
                 if "is_pred" in out:
                     predictions.append(out["is_pred"])
+                # snapshot grids of this batch under the EMA weights and the fixed noise (reference trainer.py:478-485,
+                # which passes the epoch as the file number); rank 0 only, no collective inside
+                if (self.display_interval > 0 and self.gen_iterations % self.display_interval == 0 and self.rank == 0
+                        and getattr(self, "image_dir", None)):
+                    self.save_img_results(batch, self.fixed_noise, epoch, name='average')
                 if log_now and self.rank == 0:
                     msg = ' '.join('%s: %.2f' % (k, float(v)) for k, v in out.items()
                                    if torch.is_tensor(v) and v.dim() == 0)
