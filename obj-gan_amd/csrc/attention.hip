@@ -552,7 +552,8 @@ __global__ __launch_bounds__(256) void bce_const_fwd_kernel(const float* __restr
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float v = p[i];
-        const float l1 = fmaxf(logf(v), -100.f), l0 = fmaxf(logf(1.f - v), -100.f);
+        // log1pf(-v), as torch: logf(1.f - v) is 0 for every v below 2^-24, where the term is v
+        const float l1 = fmaxf(logf(v), -100.f), l0 = fmaxf(log1pf(-v), -100.f);
         s -= t * l1 + (1.f - t) * l0;
     }
     s = og_block_sum(s, red);
