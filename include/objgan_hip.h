@@ -122,6 +122,15 @@ long objgan_conv_igemm_ws_floats(int N, int C, int H, int W, int upsample, int p
                                  int Cout, int Cin, int Torig, int transpose, int Tg,
                                  int PH, int PW, int stride, int OHf, int OWf, int osh, int osw,
                                  int act, int y_prezeroed, int math, int ring);
+/* The launch plan objgan_conv_igemm follows for the same arguments (host-only, launches nothing; for tests and tools):
+ * out[0..10] <- {bank layout class, kernel math, nw (waves per workgroup), ng (pixel groups per wave), TM (32-row groups
+ * per block row of the main launch), full_rows (its block rows), rest (height of the second launch's one block row, 0:
+ * none), tiles_n (pixel tiles), splits (K), full_cover, direct (1: a block row of height 1 runs the LDS-free instance)}.
+ * Classes 0 and 2 have no such plan: the fields behind the class are 0.  Returns 0 where the call would refuse. */
+int objgan_conv_igemm_plan(int N, int C, int H, int W, int upsample, int pad_mode,
+                           int Cout, int Cin, int Torig, int transpose, int Tg,
+                           int PH, int PW, int stride, int OHf, int OWf, int osh, int osw,
+                           int act, int y_prezeroed, int math, int ring, int* out);
 /* ring (may be NULL): data gradient of a ReflectionPad2d(1) convolution without the padded intermediate -- the
  * GEMM runs over the padded pixel grid (PH = OHf + 2, PW = OWf + 2, y is the UNPADDED gradient), interior
  * pixels are stored into y, the one-pixel border into ring [N*M][2*PW + 2*PH]; objgan_reflect_ring_fold then
@@ -135,6 +144,8 @@ int objgan_reflect_ring_fold(const float* ring, float* y, long planes, int H, in
  * then the partial maxima of |w| the fp16x2 pack leaves for its scale); wt_packed as above.
  * ws: objgan_conv_dgrad_s2_phases_ws_floats floats (math 1: the bf16 channel-blocked copy of dY, see objgan_conv_igemm; else 0). */
 long objgan_conv_dgrad_s2_phases_ws_floats(int N, int Cout, int OH, int OW, int math);
+/* the plan of its one four-phase launch, fields as objgan_conv_igemm_plan (host-only) */
+int objgan_conv_dgrad_s2_phases_plan(int N, int Cout, int OH, int OW, int Cin, int Tg, int PH, int PW, int math, int* out);
 /* Data gradient of a 4x4 / stride-2 / pad-1 convolution w.r.t. an input of Cin <= 32 channels (the first convolution of the
  * shape / object discriminators, reference model.py:1119-1128, 1217-1220), all four output parity phases in ONE launch of the
  * fp32 VALU kernel: dy [N, Cout, OH, OW] is read twice (the per-phase form read it four times), dx [N, Cin, 2 OH, 2 OW] is fully
@@ -156,6 +167,11 @@ int objgan_conv_dgrad_s2_phases(const float* x, const float* w, float* y, float*
  * workspace the call gathers the fp32 tensors and rounds them in registers (same values). */
 long objgan_conv_wgrad_ws_floats(int N, int Cin, int H, int W, int upsample, int pad_mode,
                                  int Cout, int OH, int OW, int ksize, int stride, int pad, int math);
+/* The launch plan objgan_conv_wgrad follows for the same arguments (host-only, launches nothing; for tests and tools):
+ * out[0..9] <- {rc (1: a plan follows), kmath, v2, bfb, rec, rec2, dyp, h2, xrows, nparts}, then for each of three parts
+ * (one launch each; unused parts 0) {tm, rows, cfg, m_begin, m_end, xr_count, nw, use3, b128, tiles_n, splits}: 43 ints. */
+int objgan_conv_wgrad_plan(int N, int Cin, int H, int W, int upsample, int pad_mode,
+                           int Cout, int OH, int OW, int ksize, int stride, int pad, int math, int* out);
 int objgan_conv_wgrad(const float* x, const float* dy, float* dw,
                       int N, int Cin, int H, int W, int upsample, int pad_mode,
                       int Cout, int OH, int OW, int ksize, int stride, int pad, int math,

@@ -27,8 +27,8 @@
 //             registers, filter rows via LDS; launched here (launch_igemm2), its record instances in conv_igemm_rec.hip
 // Kernels in this file: bias_act_kernel, reflect_ring_fold_kernel (splitk_combine_kernel: conv_igemm_pack.hip).
 // Host: igemm2_plan (pure: block rows, waves, splits), run_igemm2, launch_igemm2.  Entry points: objgan_conv_igemm,
-// objgan_conv_igemm_ws_floats, objgan_conv_dgrad_s2_phases, objgan_conv_dgrad_s2_phases_ws_floats,
-// objgan_reflect_ring_fold.  The weight gradient lives in conv_igemm_wgrad.hip.
+// objgan_conv_igemm_ws_floats, objgan_conv_igemm_plan, objgan_conv_dgrad_s2_phases, objgan_conv_dgrad_s2_phases_ws_floats,
+// objgan_conv_dgrad_s2_phases_plan, objgan_reflect_ring_fold.  The weight gradient lives in conv_igemm_wgrad.hip.
 #include "conv_igemm_host.h"
 
 // y[n, m, i] = act(y[n, m, i] + bias[m]) -- epilogue of the split-K path
@@ -269,6 +269,31 @@ static int run_igemm2(IgemmArgs a, hipStream_t s, float* ws, long ws_floats, flo
     return og_launch_status();
 }
 
+// Geometry and arithmetic fields of the four-phase launch (everything igemm2_plan reads; the pointers and taps are the
+// caller's): shared by objgan_conv_dgrad_s2_phases and its plan query.
+static void og_phases_args(IgemmArgs& a, int N, int Cout, int OH, int OW, int Cin, int Tg, int PH, int PW, int math) {
+    const int M = Cin, C = Cout;
+    const int Cp = (C + 15) / 16 * 16;
+    const int Kpad = Tg * Cp;
+    a.x = nullptr; a.wt = nullptr; a.bias = nullptr; a.y = nullptr;
+    a.N = N; a.C = C; a.H = OH; a.W = OW; a.LH = OH; a.LW = OW;
+    a.M = M; a.Mpad = (M + 127) / 128 * 128; a.K = C * Tg; a.Kpad = Kpad; a.T = Tg; a.Cp = Cp;
+    a.kgroup = og_kgroup_phases(C);
+    a.math = math; a.Krow = og_krow(Kpad, math); a.xmax = nullptr; a.wmax = nullptr;
+    a.nhwc = igemm2_nhwc_floats(math, N, OH, OW, Cp) > 0 ? 1 : 0;
+    a.m_begin = 0; a.m_end = M;
+    a.PH = PH; a.PW = PW; a.OHf = 2 * PH; a.OWf = 2 * PW;
+    a.osh = 2; a.osw = 2; a.ooh = 0; a.oow = 0;
+    a.stride = 1; a.pad_mode = 0; a.upsample = 0; a.act = OG_ACT_NONE;
+    a.ksplit_steps = 0;
+    a.ring = nullptr;
+    a.ws = nullptr; a.ws_stride = 0;
+    a.nphase = 4;
+#ifdef OG_DEV
+    a.ablate = og_ablate();
+#endif
+}
+
 extern "C" {
 
 // General entry: see the formula at the top of this file.
@@ -354,6 +379,41 @@ long objgan_conv_igemm_ws_floats(int N, int C, int H, int W, int upsample, int p
     return igemm2_ws_floats(a, igemm2_plan(a));
 }
 
+// out[0..10] <- {bank layout class, kernel math, nw, ng, TM, full_rows, rest, tiles_n, splits, full_cover, direct} of a
+// launch plan (direct: the block rows of height 1 run the LDS-free instance); a class without a plan (0 first
+// generation, 2 thin VALU) leaves the fields behind the class at 0.
+static void og_plan_fields(int cls, const IgemmArgs& a, int* out) {
+    for (int i = 0; i < 11; ++i) out[i] = 0;
+    out[0] = cls;
+    if (cls == 0 || cls == 2) return;
+    const Igemm2Plan q = igemm2_plan(a);
+    const int f[10] = {a.math, q.nw, q.ng, q.TM, q.full_rows, q.rest, q.tiles_n, q.splits, q.full_cover,
+                       (q.nw != 8 && a.M <= 32 && (q.TM == 1 || q.rest == 1)) ? 1 : 0};
+    for (int i = 0; i < 10; ++i) out[1 + i] = f[i];
+}
+
+// The launch plan objgan_conv_igemm follows for these arguments (those of objgan_conv_igemm_ws_floats), for tests and
+// tools: which block rows, waves, pixel groups and splits.  Host-only, launches nothing.  OG_BAD_ARGS where the call
+// itself would refuse the arguments.
+int objgan_conv_igemm_plan(int N, int C, int H, int W, int upsample, int pad_mode,
+                           int Cout, int Cin, int Torig, int transpose, int Tg,
+                           int PH, int PW, int stride, int OHf, int OWf, int osh, int osw,
+                           int act, int y_prezeroed, int math, int ring, int* out) {
+    PackArgs p;
+    IgemmArgs a;
+    int MT = 32;
+    int zeros[OG_MAX_TAPS] = {0};
+    float dummy = 0.f;
+    if (!out) return OG_BAD_ARGS;
+    memset(&p, 0, sizeof(p));
+    const int rc = og_igemm_setup(p, a, MT, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, upsample, pad_mode, Cout, Cin,
+                                  Torig, transpose, Tg, zeros, zeros, zeros, PH, PW, stride, OHf, OWf, osh, osw, 0, 0, act,
+                                  math, ring ? &dummy : nullptr);
+    if (rc != OG_OK) return OG_BAD_ARGS;
+    og_plan_fields(p.m_major, a, out);
+    return OG_OK;
+}
+
 int objgan_conv_igemm(const float* x, const float* w, const float* bias, float* y, float* wt,
                       int N, int C, int H, int W, int upsample, int pad_mode,
                       int Cout, int Cin, int Torig, int transpose,
@@ -419,23 +479,9 @@ int objgan_conv_dgrad_s2_phases(const float* x, const float* w, float* y, float*
         }
     }
     IgemmArgs a;
-    a.x = x; a.wt = wt; a.bias = nullptr; a.y = y;
-    a.N = N; a.C = C; a.H = OH; a.W = OW; a.LH = OH; a.LW = OW;
-    a.M = M; a.Mpad = (M + 127) / 128 * 128; a.K = C * Tg; a.Kpad = Kpad; a.T = Tg; a.Cp = Cp;
-    a.kgroup = og_kgroup_phases(C);
-    a.math = math; a.Krow = Krow; a.xmax = xmax; a.wmax = wt + og_phase_wmax_offset(M, Tg, Cp);
-    a.nhwc = igemm2_nhwc_floats(math, N, OH, OW, Cp) > 0 ? 1 : 0;
-    a.m_begin = 0; a.m_end = M;
-    a.PH = PH; a.PW = PW; a.OHf = 2 * PH; a.OWf = 2 * PW;
-    a.osh = 2; a.osw = 2; a.ooh = 0; a.oow = 0;
-    a.stride = 1; a.pad_mode = 0; a.upsample = 0; a.act = OG_ACT_NONE;
-    a.ksplit_steps = 0;
-    a.ring = nullptr;
-    a.ws = nullptr; a.ws_stride = 0;
-    a.nphase = 4;
-#ifdef OG_DEV
-    a.ablate = og_ablate();
-#endif
+    og_phases_args(a, N, Cout, OH, OW, Cin, Tg, PH, PW, math);
+    a.x = x; a.wt = wt; a.y = y;
+    a.xmax = xmax; a.wmax = wt + og_phase_wmax_offset(M, Tg, Cp);
     for (int t = 0; t < OG_MAX_TAPS; ++t) a.tap[t] = 0;
     for (int ph = 0; ph < 4; ++ph)
         for (int t = 0; t < Tg; ++t)
@@ -446,6 +492,19 @@ int objgan_conv_dgrad_s2_phases(const float* x, const float* w, float* y, float*
 // floats of workspace objgan_conv_dgrad_s2_phases takes (bf16 mode: the channel-blocked bf16 copy of dY; else 0)
 long objgan_conv_dgrad_s2_phases_ws_floats(int N, int Cout, int OH, int OW, int math) {
     return igemm2_nhwc_floats(math, N, OH, OW, (Cout + 15) / 16 * 16);
+}
+
+// The launch plan of objgan_conv_dgrad_s2_phases (the nphase = 4 launch), fields as objgan_conv_igemm_plan.  Host-only.
+int objgan_conv_dgrad_s2_phases_plan(int N, int Cout, int OH, int OW, int Cin, int Tg, int PH, int PW, int math, int* out) {
+    if (!out || Tg < 1 || Tg > 8) return OG_BAD_ARGS;
+    if (math < 0 || math > 5 || math == 3) return OG_BAD_ARGS;
+    if (N <= 0 || PH <= 0 || PW <= 0 || Cin <= 0 || Cout <= 0) return OG_BAD_ARGS;
+    const int Cp = (Cout + 15) / 16 * 16;
+    if ((double)N * Cout * OH * OW * 4.0 >= 4.0e9 || (double)Cin * Tg * Cp * 4.0 >= 4.0e9) return OG_BAD_ARGS;
+    IgemmArgs a;
+    og_phases_args(a, N, Cout, OH, OW, Cin, Tg, PH, PW, math);
+    og_plan_fields(math == 1 ? 3 : (math == 2 ? 4 : (math >= 4 ? 5 : 1)), a, out);
+    return OG_OK;
 }
 
 // y [planes, H, W] += mirror of ring [planes, 2*(W+2) + 2*(H+2)] (written by objgan_conv_igemm in ring mode).

@@ -12,7 +12,8 @@
 //   conv_wgrad_kernel (conv_igemm_v1.hip)   maps whose width is not a multiple of 8, tensors beyond 2 GiB
 //   wgrad_combine_kernel             the second level of the pixel split
 // Host: og_wgrad_plan (pure: form, operand copies, parts, workspace), launch_wgrad2; objgan_conv_wgrad walks the parts.
-// Entry points: objgan_conv_wgrad, objgan_conv_wgrad_ws_floats, objgan_conv_wgrad_rec_ok, objgan_conv_wgrad_bfb_ok.
+// Entry points: objgan_conv_wgrad, objgan_conv_wgrad_ws_floats, objgan_conv_wgrad_plan, objgan_conv_wgrad_rec_ok,
+// objgan_conv_wgrad_bfb_ok.
 #include "conv_igemm_host.h"
 
 // dw rows <- sum over the splits of a weight-gradient launch (WgradArgs::ws): local row r of the slot is dw row
@@ -1315,6 +1316,27 @@ long objgan_conv_wgrad_ws_floats(int N, int Cin, int H, int W, int upsample, int
                                  int Cout, int OH, int OW, int ksize, int stride, int pad, int math) {
     const WgradPlan p = og_wgrad_plan(N, Cin, H, W, upsample, pad_mode, Cout, OH, OW, ksize, stride, math, true);
     return p.rc == OG_OK ? p.total : 0;
+}
+
+// The launch plan objgan_conv_wgrad follows for these arguments (those of objgan_conv_wgrad_ws_floats, planned with a
+// workspace), for tests and tools.  out[0..9] <- {rc, kmath, v2, bfb, rec, rec2, dyp, h2, xrows, nparts}, then 11 ints
+// per part for three parts (unused parts 0): {tm, rows, cfg, m_begin, m_end, xr_count, nw, use3, b128, tiles_n, splits}.
+// Host-only, launches nothing.
+int objgan_conv_wgrad_plan(int N, int Cin, int H, int W, int upsample, int pad_mode,
+                           int Cout, int OH, int OW, int ksize, int stride, int pad, int math, int* out) {
+    if (!out) return OG_BAD_ARGS;
+    const WgradPlan p = og_wgrad_plan(N, Cin, H, W, upsample, pad_mode, Cout, OH, OW, ksize, stride, math, true);
+    for (int i = 0; i < 10 + 3 * 11; ++i) out[i] = 0;
+    out[0] = p.rc;
+    if (p.rc != OG_OK) return OG_OK;
+    const int head[9] = {p.kmath, p.v2, p.bfb, p.rec, p.rec2, p.dyp, p.h2, p.xrows, p.nparts};
+    for (int i = 0; i < 9; ++i) out[1 + i] = head[i];
+    for (int i = 0; i < p.nparts; ++i) {
+        const WgradPart& q = p.part[i];
+        const int f[11] = {q.tm, q.rows, q.cfg, q.m_begin, q.m_end, q.xr_count, q.nw, q.use3, q.b128, q.tiles_n, q.splits};
+        for (int j = 0; j < 11; ++j) out[10 + 11 * i + j] = f[j];
+    }
+    return OG_OK;
 }
 
 // 1 if objgan_conv_wgrad takes math 5 (x as its fp16 record, see objgan_h2_records) for this geometry.  Host-only.

@@ -94,6 +94,10 @@ SIGNATURES = {
     "objgan_conv_bank_layout": [_c_int] * 10,
     "objgan_conv_wgrad_rec_ok": [_c_int] * 8,
     "objgan_conv_wgrad_bfb_ok": [_c_int] * 8,
+    # launch-plan queries (host-only; they return 1 / 0 like every entry point and fill an int array)
+    "objgan_conv_igemm_plan": [_c_int] * 22 + [_ptr],
+    "objgan_conv_dgrad_s2_phases_plan": [_c_int] * 9 + [_ptr],
+    "objgan_conv_wgrad_plan": [_c_int] * 13 + [_ptr],
     "objgan_nhwc_bf16": [_ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
     "objgan_prof_collect": [_ptr, _ptr, _ptr],
     "objgan_prof_dump": [_ptr, _ptr, _ptr, _c_int, _ptr],

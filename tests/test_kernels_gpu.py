@@ -681,10 +681,12 @@ def test_rnn_encoder_matches_oracle_and_reference_golden(dev):
 
 BF16_CASES = [
     # N, Cin, H, W, Cout, k, stride, pad, pad_mode, upsample
-    (2, 194, 16, 16, 388, 3, 1, 1, "reflect", False),     # two block rows (7 + 6 groups), odd chunk count
+    # 13 forward block rows of one row group each, split along K; the weight gradient in two parts (7 + 6 row groups);
+    # odd chunk count
+    (2, 194, 16, 16, 388, 3, 1, 1, "reflect", False),
     (2, 194, 8, 8, 96, 3, 1, 1, "zeros", True),           # upBlock
     (2, 96, 16, 16, 192, 4, 2, 1, "zeros", False),        # D encoder, phased dgrad
-    (2, 40, 16, 24, 40, 3, 1, 1, "zeros", False),         # short tiles (TM = 2): LDS-free weight-gradient form
+    (2, 40, 16, 24, 40, 3, 1, 1, "zeros", False),         # weight gradient on a short tile (tm = 2): LDS-free form
     (3, 256, 12, 1, 48, 1, 1, 0, "zeros", False),         # 1x1
 ]
 
@@ -740,7 +742,7 @@ X3_CASES = [
 
 
 @pytest.mark.parametrize("case", BF16_CASES + [
-    (4, 96, 64, 64, 192, 4, 2, 1, "zeros", False),        # large enough for unsplit launches and 8-wave workgroups
+    (4, 96, 64, 64, 192, 4, 2, 1, "zeros", False),        # forward TM 1 in 6 K splits, four-phase data gradient; 4 waves
     (2, 194, 64, 64, 194, 3, 1, 1, "reflect", False),
     (2, 194, 32, 32, 96, 3, 1, 1, "zeros", True),
 ])
@@ -776,12 +778,17 @@ def test_bf16_blocked_operand_equals_the_fp32_gather_form(dev, case):
 REC_CASES = BF16_CASES + [
     (1, 7, 13, 10, 130, 3, 2, 1, "zeros", False),          # odd sizes, stride 2, k3: per-phase launches into a pre-zeroed dX
     (3, 200, 4, 4, 40, 4, 2, 0, "zeros", False),           # small grid: split-K through the workspace
-    (4, 96, 64, 64, 192, 4, 2, 1, "zeros", False),         # unsplit launches, 8-wave workgroups
+    # forward TM 1 x 6 block rows in 6 K splits, unsplit four-phase data gradient (TM 1 x 3), weight gradient tm 6 in
+    # 8 pixel splits: 4-wave workgroups throughout
+    (4, 96, 64, 64, 192, 4, 2, 1, "zeros", False),
     (2, 194, 64, 64, 194, 3, 1, 1, "reflect", False),      # ring form of the reflect-pad data gradient
-    # large enough for two pixel groups per wave (>= 512 workgroups of 256 pixels at block-row heights <= 3)
+    # two pixel groups per wave in the ring data gradient (TM 1 x 2 block rows, 529 tiles of 256 pixels: >= the 1024
+    # workgroups of og_rec_ng2_min); the forward (TM 3, 1024 tiles of 128 pixels) keeps one group
     (8, 64, 128, 128, 96, 3, 1, 1, "reflect", False),
-    (8, 96, 256, 256, 192, 4, 2, 1, "zeros", False),       # four-phase data gradient, 96-row tiles
-    (8, 194, 128, 128, 96, 3, 1, 1, "zeros", True),        # upBlock on the transposed 4x4 form, ragged channel chunk
+    (8, 96, 256, 256, 192, 4, 2, 1, "zeros", False),       # four-phase data gradient, 96-row tiles; forward TM 6 on 8 waves
+    # upBlock, ragged channel chunk: on the transposed 4x4 form where the call has no activation; with the fused
+    # LeakyReLU of the bit-identity test the plain up-sampling gather, two pixel groups per wave (TM 3)
+    (8, 194, 128, 128, 96, 3, 1, 1, "zeros", True),
     (16, 194, 32, 32, 388, 3, 1, 1, "reflect", False),     # small reflect-padded maps: the weight gradient on records
 ]
 
