@@ -209,6 +209,28 @@ int objgan_lstm_bidir_forward(const float* table, const long* captions, const in
                               const float* wt_ih, const float* wt_hh, const float* b_ih, const float* b_hh,
                               float* out, float* hn, int B, int L, int Lout, int I, int H, int ntoken,
                               void* stream);
+/* the same pass, also returning the final cell state cn [B][2H] (layout of hn) */
+int objgan_lstm_bidir_forward_state(const float* table, const long* captions, const int* lens,
+                                    const float* wt_ih, const float* wt_hh, const float* b_ih, const float* b_hh,
+                                    float* out, float* hn, float* cn, int B, int L, int Lout, int I, int H,
+                                    int ntoken, void* stream);
+
+/* ---- box generator, sampling path (reference box_generation DecoderRNN.forward_step, is_training=0): one launch
+ * decodes B captions from the encoder's (h_n, c_n) to label / box sequences of <= T steps.  h0, c0 [B][H];
+ * noise [B][T][6] doubles (uniform, normal, normal for the xy draw, then for the wh draw).  l_emb [L][H]; xy_w, wh_w,
+ * nxy_w [A][2] with biases [A]; wt_ih [2A+H][4H], wt_hh [H][4H], lo_wt [H][L], xyo_wt [H+L][6K], who_wt [H+L+A][6K] are
+ * transposed nn weights.  Limits: 4H <= 1024, L <= 256, K <= 8, T <= 32, A <= 64, cpw in {1, 2, 4, 8} with the
+ * tile's state within 64 KiB of LDS.  labels [B][T] int32, lengths [B] int32, samples [B][T][4] doubles (x, y, w, h),
+ * trace (nullable) [B][T][L + 12K]; entries past a caption's length are zero. */
+int objgan_box_decode_default_cpw(void);
+int objgan_box_decode(const float* h0, const float* c0, const double* noise,
+                      const float* l_emb, const float* xy_w, const float* xy_b, const float* wh_w, const float* wh_b,
+                      const float* nxy_w, const float* nxy_b, const float* wt_ih, const float* wt_hh,
+                      const float* b_ih, const float* b_hh, const float* lo_wt, const float* lo_b,
+                      const float* xyo_wt, const float* xyo_b, const float* who_wt, const float* who_b,
+                      float x0, float y0, float w0, float r0,
+                      int* labels, int* lengths, double* samples, float* trace,
+                      int B, int T, int H, int L, int K, int A, int sos, int eos, int cpw, void* stream);
 
 /* ---- normalisation + GLU / LeakyReLU / residual (BatchNorm train mode, InstanceNorm) -------- */
 /* `sums` (forward) / `bsums` (backward): statistics workspace of objgan_norm_ws_floats(N, C, HW, per_channel) floats

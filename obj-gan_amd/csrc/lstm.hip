@@ -18,7 +18,7 @@ __global__ void lstm_bidir_fwd_kernel(const float* __restrict__ table, const lon
                                       const int* __restrict__ lens,
                                       const float* __restrict__ wt_ih, const float* __restrict__ wt_hh,
                                       const float* __restrict__ b_ih, const float* __restrict__ b_hh,
-                                      float* __restrict__ out, float* __restrict__ hn,
+                                      float* __restrict__ out, float* __restrict__ hn, float* __restrict__ cn,
                                       int L, int Lout, int I, int H, int ntoken) {
     extern __shared__ float sm[];
     float* xs = sm;             // [I]
@@ -67,7 +67,24 @@ __global__ void lstm_bidir_fwd_kernel(const float* __restrict__ table, const lon
         }
     }
     __syncthreads();
-    if (j < H) hn[(size_t)b * 2 * H + dir * H + j] = hs[j];
+    if (j < H) {
+        hn[(size_t)b * 2 * H + dir * H + j] = hs[j];
+        if (cn) cn[(size_t)b * 2 * H + dir * H + j] = cs[j];      // the box decoder starts from (h_n, c_n)
+    }
+}
+
+static int lstm_bidir_launch(const float* table, const long* captions, const int* lens,
+                             const float* wt_ih, const float* wt_hh, const float* b_ih, const float* b_hh,
+                             float* out, float* hn, float* cn, int B, int L, int Lout, int I, int H, int ntoken,
+                             void* stream) {
+    if (4 * H > 1024 || H < 1 || I < 1 || L < 1 || Lout < 1 || ntoken < 1) return OG_BAD_ARGS;
+    if (B <= 0) return OG_OK;
+    const int threads = (4 * H + 63) / 64 * 64;
+    const size_t lds = sizeof(float) * (size_t)(I + 6 * H);
+    if (lds > 64 * 1024) return OG_BAD_ARGS;
+    hipLaunchKernelGGL(lstm_bidir_fwd_kernel, dim3(B, 2), dim3(threads), lds, (hipStream_t)stream,
+                       table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, out, hn, cn, L, Lout, I, H, ntoken);
+    return og_launch_status();
 }
 
 extern "C" {
@@ -80,14 +97,20 @@ int objgan_lstm_bidir_forward(const float* table, const long* captions, const in
                               float* out, float* hn, int B, int L, int Lout, int I, int H, int ntoken,
                               void* stream) {
     OG_ENTRY();
-    if (4 * H > 1024 || H < 1 || I < 1 || L < 1 || Lout < 1 || ntoken < 1) return OG_BAD_ARGS;
-    if (B <= 0) return OG_OK;
-    const int threads = (4 * H + 63) / 64 * 64;
-    const size_t lds = sizeof(float) * (size_t)(I + 6 * H);
-    if (lds > 64 * 1024) return OG_BAD_ARGS;
-    hipLaunchKernelGGL(lstm_bidir_fwd_kernel, dim3(B, 2), dim3(threads), lds, (hipStream_t)stream,
-                       table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, out, hn, L, Lout, I, H, ntoken);
-    return og_launch_status();
+    return lstm_bidir_launch(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, out, hn, nullptr,
+                             B, L, Lout, I, H, ntoken, stream);
+}
+
+// The same pass, also returning the final cell state cn [B][2H] (layout of hn): the box decoder's initial state is
+// (h_n, c_n) of both directions (reference box_generation DecoderRNN._cat_directions).
+int objgan_lstm_bidir_forward_state(const float* table, const long* captions, const int* lens,
+                                    const float* wt_ih, const float* wt_hh, const float* b_ih, const float* b_hh,
+                                    float* out, float* hn, float* cn, int B, int L, int Lout, int I, int H,
+                                    int ntoken, void* stream) {
+    OG_ENTRY();
+    if (!cn) return OG_BAD_ARGS;
+    return lstm_bidir_launch(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, out, hn, cn,
+                             B, L, Lout, I, H, ntoken, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@ training path reads:
   <data_dir>/<split>_gt_insanns.pickle [ {key: {'rois', 'fm_rois', 'masks', 'bbox maps',
                                                'bbox fmaps', 'num_rois', ...}} ]
   <data_dir>/<split>/class_info.pickle optional class ids
+  <data_dir>/gen_masks/<key>/<i>/boxes.txt  layouts of the box generator (sample.py), "x,y,w,h,label,0" per line;
+                                      <split>_gen_insanns.pickle is built from them when it is missing
 
 Building those files from raw COCO (captions via nltk / spacy / torchtext, masks via
 pycocotools) is preprocessing, not the training path: where a prepared file is missing the
@@ -213,8 +215,81 @@ def load_class_id(data_dir, total_num):
 def load_anns_data(data_dir, split, postfix, ann_type, filenames, imsize, fmsize, cats_index_dict):
     filepath = os.path.join(data_dir, '%s%s' % (split, postfix))
     if not os.path.isfile(filepath):
-        raise FileNotFoundError("%s: build it with the reference's preprocessing (pycocotools)" % filepath)
+        if ann_type == 'gen' and os.path.isdir(os.path.join(data_dir, 'gen_masks')):
+            # layouts written by sample.py (or by the reference's box generator): build the pickle as the reference does
+            insanns_dict = load_gen_insanns(data_dir, filenames, split, imsize, fmsize, cats_index_dict)
+            with open(filepath, 'wb') as f:
+                pickle.dump([insanns_dict], f, protocol=2)
+            print('Save to: ', filepath)
+            return insanns_dict
+        raise FileNotFoundError("%s: build it with the reference's preprocessing (pycocotools)%s" % (
+            filepath, ", or run sample.py to write <data_dir>/gen_masks/" if ann_type == 'gen' else ""))
     return _load_pickle(filepath, encoding='latin1')[0]
+
+
+def _read_boxes(path):
+    """`boxes.txt` rows `x,y,w,h,label,crowd` as integers, fractions dropped toward zero (the reference reads them with
+    pandas.read_csv(header=None).astype(int)); None for a missing or empty file."""
+    if not (os.path.isfile(path) and os.path.getsize(path) > 0):
+        return None
+    with open(path) as f:
+        rows = [[int(float(v)) for v in ln.split(',')] for ln in f.read().splitlines() if ln.strip()]
+    return np.array(rows, dtype=np.int64) if rows else None
+
+
+def load_gen_insanns(data_dir, filenames, split, imsize, fmsize, cats_index_dict):
+    """{key: {caption index: annotation dictionary}} from `<data_dir>/gen_masks/<key>/<i>/boxes.txt` (reference
+    load.py:653-776): boxes with both sides under ROI_MIN_SIZE dropped, the BOXES_NUM largest kept, rois per branch
+    scale, feature-map rois and the two stacks of box maps; a caption without a usable box has num_rois 0 and no maps."""
+    print('creating %s gen_insanns' % split)
+    gen_dir = os.path.join(data_dir, 'gen_masks')
+    nb, R, D = cfg.TREE.BRANCH_NUM, cfg.ROI.BOXES_NUM, cfg.ROI.BOXES_DIM
+    scales = [imsize[b] / float(imsize[-1]) for b in range(nb)]
+    insanns_dict = {}
+    for key in filenames:
+        key_dir = os.path.join(gen_dir, key)
+        indices = sorted(int(name) for name in os.listdir(key_dir)) if os.path.isdir(key_dir) else []
+        anno_dicts = {}
+        for index in indices:
+            boxes = _read_boxes(os.path.join(key_dir, str(index), 'boxes.txt'))
+            rois = [np.zeros((R, D)) for _ in range(nb)]
+            fm_rois = np.zeros((R, D))
+            anno = {'rois': rois, 'fm_rois': fm_rois, 'bbox maps': None, 'bbox fmaps': None, 'num_rois': 0}
+            anno_dicts[index] = anno
+            if boxes is None:
+                continue
+            keep = [r for r in boxes if not (r[2] < cfg.ROI.ROI_MIN_SIZE and r[3] < cfg.ROI.ROI_MIN_SIZE)]
+            if not keep:
+                continue
+            raw_rois = np.zeros((len(keep), 6))
+            for n, r in enumerate(keep):
+                raw_rois[n, :4] = r[:4]
+                raw_rois[n, 4] = cats_index_dict[int(r[4])]
+            if len(keep) > R:                                  # the largest boxes first, as utils.calc_sort_size
+                order = np.argsort(np.multiply(raw_rois[:, 2], raw_rois[:, 3]))[::-1].tolist()
+                raw_rois = raw_rois[order, :][:R, :]
+            num_rois = raw_rois.shape[0]
+            for b in range(nb):
+                rois[b][:num_rois, :] = raw_rois
+                rois[b][:, [0, 2]] = rois[b][:, [0, 2]] * scales[b]
+                rois[b][:, [1, 3]] = rois[b][:, [1, 3]] * scales[b]
+            fm_rois[:num_rois, :] = rois[0][:num_rois, :].copy()
+            fm_rois[:, :4] = fm_rois[:, :4] / 2.0
+            maps = np.zeros((num_rois, imsize[0], imsize[0]))
+            fmaps = np.zeros((num_rois, fmsize, fmsize))
+            for r in range(num_rois):
+                x, y, w, h = rois[0][r, :4]
+                x0, y0 = min(int(round(x)), imsize[0] - 1), min(int(round(y)), imsize[0] - 1)
+                x1, y1 = min(int(round(x + w)), imsize[0] - 1), min(int(round(y + h)), imsize[0] - 1)
+                maps[r, y0:y1, x0:x1] = 1
+                x, y, w, h = fm_rois[r, :4]
+                x0, y0 = min(int(round(x / 2.0)), fmsize - 1), min(int(round(y / 2.0)), fmsize - 1)
+                x1 = min(int(round(x / 2.0 + w / 2.0)), fmsize - 1)
+                y1 = min(int(round(y / 2.0 + h / 2.0)), fmsize - 1)
+                fmaps[r, y0:y1, x0:x1] = 1
+            anno.update({'bbox maps': maps, 'bbox fmaps': fmaps, 'num_rois': num_rois})
+        insanns_dict[key] = anno_dicts
+    return insanns_dict
 
 
 # ---------------------------------------------------------------------------------------------

@@ -40,6 +40,9 @@ SIGNATURES = {
                           _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_long, _ptr],
     "objgan_lstm_bidir_forward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                   _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr],
+    "objgan_lstm_bidir_forward_state": [_ptr] * 10 + [_c_int] * 6 + [_ptr],
+    "objgan_box_decode_default_cpw": [],
+    "objgan_box_decode": [_ptr] * 20 + [_c_float] * 4 + [_ptr] * 4 + [_c_int] * 9 + [_ptr],
     "objgan_norm_forward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                             _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _ptr, _ptr],
     "objgan_norm_amax_supported": [_c_int] * 5,

@@ -25,8 +25,10 @@ if os.environ.get("OBJGAN_DEV") == "1":
 # reference-signature objgan_roi_align_backward (unordered scatter, as the CUDA original).  The convolution files carry
 # no fp32 atomic any more (round 5: the first-generation split-K path is gone); the training step runs without any.
 # The snapshot grids round (x + 1) / 2 * 255 and (v - min) / (max - min) * 255 operation by operation, like numpy.
+# The box decoder's mixture draw rounds its fp32 products one by one, as the reference's host code does; its dot
+# products call fmaf explicitly.
 PER_FILE_FLAGS = {"roi_align.hip": ["-ffp-contract=off", "-munsafe-fp-atomics"], "resize_pil.hip": ["-ffp-contract=off"],
-                  "snapshot.hip": ["-ffp-contract=off"]}
+                  "snapshot.hip": ["-ffp-contract=off"], "box_decode.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

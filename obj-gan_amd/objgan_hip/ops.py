@@ -2169,9 +2169,10 @@ def lift_stem_conv(seg, w, bias, size):
 # ----------------------------------------------------------------------------------------------
 # frozen text encoder
 # ----------------------------------------------------------------------------------------------
-def lstm_bidir_forward(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, max_len):
+def lstm_bidir_forward(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, max_len, return_cn=False):
     """Embedding + bidirectional LSTM over packed captions -> (words_emb [B, 2H, max_len],
-    sent_emb [B, 2H]); forward only (the encoder is frozen on the training path)."""
+    sent_emb [B, 2H]); forward only (the encoder is frozen on the training path).  return_cn=True
+    also returns the final cell state [B, 2H] (the box decoder's initial state needs it)."""
     _chk(table, wt_ih, wt_hh, b_ih, b_hh)
     if not captions.is_cuda or captions.dtype != torch.int64:
         raise _lib.ObjganHipError("lstm: captions must be an int64 tensor on the GPU")
@@ -2182,9 +2183,56 @@ def lstm_bidir_forward(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, max_len)
     H = G // 4
     out = torch.empty((B, 2 * H, int(max_len)), dtype=_F32, device=captions.device)
     hn = torch.empty((B, 2 * H), dtype=_F32, device=captions.device)
+    if return_cn:
+        cn = torch.empty((B, 2 * H), dtype=_F32, device=captions.device)
+        _lib.call("objgan_lstm_bidir_forward_state", _p(table), _p(captions), _p(lens), _p(wt_ih), _p(wt_hh),
+                  _p(b_ih), _p(b_hh), _p(out), _p(hn), _p(cn), B, L, int(max_len), I, H, table.shape[0], _stream())
+        return out, hn, cn
     _lib.call("objgan_lstm_bidir_forward", _p(table), _p(captions), _p(lens), _p(wt_ih), _p(wt_hh),
               _p(b_ih), _p(b_hh), _p(out), _p(hn), B, L, int(max_len), I, H, table.shape[0], _stream())
     return out, hn
+
+
+# ----------------------------------------------------------------------------------------------
+# box generator, sampling path
+# ----------------------------------------------------------------------------------------------
+def box_decode_cpw():
+    """captions per workgroup of the default box_decode launch"""
+    return int(_lib.load().objgan_box_decode_default_cpw())
+
+
+def box_decode(h0, c0, noise, weights, first_input, sos, eos, trace=False, cpw=None):
+    """Decode B captions in one launch (reference box_generation DecoderRNN.forward, is_training=0).
+    h0, c0 [B, H]: the encoder's (h_n, c_n); noise [B, T, 6] float64 (uniform, normal, normal for the (x, y) draw,
+    then for the (w, h) draw).  `weights`: the 17 tensors in the order of the C entry point (l_emb, xy_w, xy_b, wh_w,
+    wh_b, nxy_w, nxy_b, wt_ih, wt_hh, b_ih, b_hh, lo_wt, lo_b, xyo_wt, xyo_b, who_wt, who_b; the *_wt transposed).
+    first_input: (x, y, w, r) of the first step.  Returns labels [B, T] int32, lengths [B] int32, samples [B, T, 4]
+    float64 and, with trace=True, the per-step label softmax and mixture parameters [B, T, L + 12K]."""
+    _chk(h0, c0, *weights)
+    if not noise.is_cuda or noise.dtype != torch.float64 or noise.dim() != 3 or noise.shape[2] != 6:
+        raise _lib.ObjganHipError("box_decode: noise must be a [B, T, 6] float64 tensor on the GPU")
+    if len(weights) != 17:
+        raise _lib.ObjganHipError("box_decode: 17 weight tensors expected")
+    h0, c0, noise = _c(h0), _c(c0), _c(noise)
+    weights = [_c(w) for w in weights]
+    B, H = h0.shape
+    T = noise.shape[1]
+    l_emb, xy_w, wt_ih, wt_hh, lo_wt, xyo_wt, who_wt = (weights[i] for i in (0, 1, 7, 8, 11, 13, 15))
+    L, A, K = l_emb.shape[0], xy_w.shape[0], xyo_wt.shape[1] // 6
+    shapes = [(L, H), (A, 2), (A,), (A, 2), (A,), (A, 2), (A,), (2 * A + H, 4 * H), (H, 4 * H), (4 * H,), (4 * H,),
+              (H, L), (L,), (H + L, 6 * K), (6 * K,), (H + L + A, 6 * K), (6 * K,)]
+    if tuple(c0.shape) != (B, H) or noise.shape[0] != B or [tuple(w.shape) for w in weights] != shapes:
+        raise _lib.ObjganHipError("box_decode: inconsistent shapes")
+    dev = h0.device
+    labels = torch.empty((B, T), dtype=torch.int32, device=dev)
+    lengths = torch.empty((B,), dtype=torch.int32, device=dev)
+    samples = torch.empty((B, T, 4), dtype=torch.float64, device=dev)
+    tr = torch.empty((B, T, L + 12 * K), dtype=_F32, device=dev) if trace else None
+    x0, y0, w0, r0 = (float(v) for v in first_input)
+    _lib.call("objgan_box_decode", _p(h0), _p(c0), _p(noise), *[_p(w) for w in weights], x0, y0, w0, r0,
+              _p(labels), _p(lengths), _p(samples), _p(tr), B, T, H, L, K, A, int(sos), int(eos),
+              box_decode_cpw() if cpw is None else int(cpw), _stream())
+    return (labels, lengths, samples, tr) if trace else (labels, lengths, samples)
 
 
 # ----------------------------------------------------------------------------------------------
