@@ -232,6 +232,36 @@ int objgan_box_decode(const float* h0, const float* c0, const double* noise,
                       int* labels, int* lengths, double* samples, float* trace,
                       int B, int T, int H, int L, int K, int A, int sos, int eos, int cpw, void* stream);
 
+/* ---- box generator, training step (csrc/box_train.hip; reference DecoderRNN.forward with is_training=1, loss.py
+ * Perplexity / BBLoss, the trainer's backward and clip).  The 17 weight tensors and their layout are those of
+ * objgan_box_decode.  labels [B][T+1] int32 and boxes [B][T+1][4] (x, y, w, r; the <sos> column first) are the
+ * targets, lens [B] int32 the decode steps of each caption (<= T).  Limits: 4H <= 1024, L <= 256, K <= 8, T <= 256,
+ * A <= 64, cpw in {1, 2, 4, 8} with the tile's state within 64 KiB of LDS.  ws: objgan_box_train_ws_floats floats,
+ * written by the forward pass and read and extended by the backward pass of the same step.
+ * forward: trace [B][T][L + 12K] in objgan_box_decode's layout, zero past each length; a caption's rows do not depend
+ *     on cpw, its place, B or T.
+ * loss: sums = 4B + 1 doubles (per caption: label term, box term, non-pad steps, arg-max matches; then sum_b n_b);
+ *     dtrace = d[(lamda1 sum label + lamda2 sum box) / sum n] / d(trace).
+ * backward: grads = HOST array of the 17 device pointers (kernel layout), every element written, bit-reproducible.
+ * clip: out[0] = max(1, (norm + 1e-6) / max_norm), out[1] = the L2 norm of the n floats at g; partials >= 256 doubles.
+ *     objgan_adam_step_gated(flag = out, grad_scale < 0) then applies clip_grad_norm_ and Adam without a host read. */
+long objgan_box_train_ws_floats(int B, int T, int H, int L, int K, int A);
+int objgan_box_train_forward(const float* h0, const float* c0, const int* labels, const float* boxes, const int* lens,
+                             const float* l_emb, const float* xy_w, const float* xy_b, const float* wh_w,
+                             const float* wh_b, const float* nxy_w, const float* nxy_b, const float* wt_ih,
+                             const float* wt_hh, const float* b_ih, const float* b_hh, const float* lo_wt,
+                             const float* lo_b, const float* xyo_wt, const float* xyo_b, const float* who_wt,
+                             const float* who_b, float x0, float y0, float w0, float r0, float* trace, float* ws,
+                             long ws_floats, int B, int T, int H, int L, int K, int A, int cpw, void* stream);
+int objgan_box_train_loss(const float* trace, const int* labels, const float* boxes, const int* lens,
+                          const float* weight, float lamda1, float lamda2, double* sums, float* dtrace,
+                          int B, int T, int L, int K, int pad, void* stream);
+int objgan_box_train_backward(const float* dtrace, const float* trace, const float* c0, const int* labels,
+                              const int* lens, const float* wt_ih, const float* wt_hh, const float* lo_wt,
+                              const float* xyo_wt, const float* who_wt, float* const* grads, float* ws, long ws_floats,
+                              int B, int T, int H, int L, int K, int A, int cpw, void* stream);
+int objgan_box_train_clip(const float* g, long n, float max_norm, double* partials, float* out, void* stream);
+
 /* ---- normalisation + GLU / LeakyReLU / residual (BatchNorm train mode, InstanceNorm) -------- */
 /* `sums` (forward) / `bsums` (backward): statistics workspace of objgan_norm_ws_floats(N, C, HW, per_channel) floats
  * (host-only query): every workgroup of the statistics launch stores its partial pair into its own slot, a second

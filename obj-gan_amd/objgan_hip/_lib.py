@@ -43,6 +43,10 @@ SIGNATURES = {
     "objgan_lstm_bidir_forward_state": [_ptr] * 10 + [_c_int] * 6 + [_ptr],
     "objgan_box_decode_default_cpw": [],
     "objgan_box_decode": [_ptr] * 20 + [_c_float] * 4 + [_ptr] * 4 + [_c_int] * 9 + [_ptr],
+    "objgan_box_train_forward": [_ptr] * 22 + [_c_float] * 4 + [_ptr, _ptr, _c_long] + [_c_int] * 7 + [_ptr],
+    "objgan_box_train_loss": [_ptr] * 5 + [_c_float] * 2 + [_ptr, _ptr] + [_c_int] * 5 + [_ptr],
+    "objgan_box_train_backward": [_ptr] * 12 + [_c_long] + [_c_int] * 7 + [_ptr],
+    "objgan_box_train_clip": [_ptr, _c_long, _c_float, _ptr, _ptr, _ptr],
     "objgan_norm_forward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                             _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _ptr, _ptr],
     "objgan_norm_amax_supported": [_c_int] * 5,
@@ -113,6 +117,7 @@ LONG_RETURN = {"objgan_conv_packed_floats": [_c_int, _c_int, _c_int],
                "objgan_h2_records_floats": [_c_int, _c_int, _c_long],
                "objgan_nhwc_bf16_floats": [_c_int, _c_int, _c_long],
                "objgan_norm_ws_floats": [_c_int] * 4,
+               "objgan_box_train_ws_floats": [_c_int] * 6,
                "objgan_attn_general_backward_ws_floats": [_c_int] * 4,
                "objgan_masked_max_backward_ws_floats": [_c_int] * 4,
                "objgan_channel_sum_ws_floats": [_c_int] * 3,

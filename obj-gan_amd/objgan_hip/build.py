@@ -28,7 +28,8 @@ if os.environ.get("OBJGAN_DEV") == "1":
 # The box decoder's mixture draw rounds its fp32 products one by one, as the reference's host code does; its dot
 # products call fmaf explicitly.
 PER_FILE_FLAGS = {"roi_align.hip": ["-ffp-contract=off", "-munsafe-fp-atomics"], "resize_pil.hip": ["-ffp-contract=off"],
-                  "snapshot.hip": ["-ffp-contract=off"], "box_decode.hip": ["-ffp-contract=off"]}
+                  "snapshot.hip": ["-ffp-contract=off"], "box_decode.hip": ["-ffp-contract=off"],
+                  "box_train.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -2236,6 +2236,139 @@ def box_decode(h0, c0, noise, weights, first_input, sos, eos, trace=False, cpw=N
 
 
 # ----------------------------------------------------------------------------------------------
+# box generator, training step
+# ----------------------------------------------------------------------------------------------
+def box_weight_shapes(H, L, K, A):
+    """shapes of the 17 tensors in the kernels' layout and order"""
+    return [(L, H), (A, 2), (A,), (A, 2), (A,), (A, 2), (A,), (2 * A + H, 4 * H), (H, 4 * H), (4 * H,), (4 * H,),
+            (H, L), (L,), (H + L, 6 * K), (6 * K,), (H + L + A, 6 * K), (6 * K,)]
+
+
+def box_arena(shapes, device, fill=None):
+    """one flat fp32 arena and its views of the given shapes (parameters, gradients and Adam moments of the box
+    generator live in such arenas: the norm, the clip and Adam each run over one contiguous range)"""
+    sizes = [int(math.prod(s)) for s in shapes]
+    flat = torch.zeros(sum(sizes), dtype=_F32, device=device)
+    views, o = [], 0
+    for s, n in zip(shapes, sizes):
+        views.append(flat[o:o + n].view(s))
+        o += n
+    if fill is not None:
+        for v, t in zip(views, fill):
+            v.copy_(t)
+    return flat, views
+
+
+def _box_train_dims(weights, name):
+    if len(weights) != 17:
+        raise _lib.ObjganHipError("%s: 17 weight tensors expected" % name)
+    L, H = weights[0].shape
+    A, K = weights[1].shape[0], weights[13].shape[1] // 6
+    if [tuple(w.shape) for w in weights] != box_weight_shapes(H, L, K, A) or any(not w.is_contiguous() for w in weights):
+        raise _lib.ObjganHipError("%s: the 17 tensors must be contiguous, in the kernel's layout" % name)
+    return H, L, K, A
+
+
+def _box_targets(labels, boxes, lens, B, name):
+    for t, dt in ((labels, torch.int32), (boxes, _F32), (lens, torch.int32)):
+        if not t.is_cuda:
+            raise _lib.ObjganHipError("%s: targets must be on the GPU (got a %s tensor); there is no CPU path"
+                                      % (name, t.device))
+        if t.dtype != dt or not t.is_contiguous():
+            raise _lib.ObjganHipError("%s: labels / lens are contiguous int32, boxes contiguous fp32" % name)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 2 or \
+            tuple(boxes.shape) != (B, labels.shape[1], 4) or tuple(lens.shape) != (B,):
+        raise _lib.ObjganHipError("%s: labels [B, T + 1], boxes [B, T + 1, 4], lens [B] expected" % name)
+    return labels.shape[1] - 1
+
+
+def box_train_ws_floats(B, T, H, L, K, A):
+    n = int(_lib.load().objgan_box_train_ws_floats(B, T, H, L, K, A))
+    if n <= 0 and B > 0:
+        raise _lib.ObjganHipError("box_train: shape outside the kernel's limits")
+    return n
+
+
+def box_train_forward(h0, c0, labels, boxes, lens, weights, first_input, ws=None, cpw=None):
+    """Teacher-forced decode of B captions (reference DecoderRNN.forward, is_training=1).  labels [B, T + 1] int32 and
+    boxes [B, T + 1, 4] fp32 are the targets (<sos> column first), lens [B] int32 the steps of each caption.
+    -> trace [B, T, L + 12K] (zero past each length) and the workspace the backward pass reads."""
+    _chk(h0, c0, *weights)
+    H, L, K, A = _box_train_dims(weights, "box_train_forward")
+    h0, c0 = _c(h0), _c(c0)
+    B = h0.shape[0]
+    if tuple(h0.shape) != (B, H) or tuple(c0.shape) != (B, H):
+        raise _lib.ObjganHipError("box_train_forward: h0, c0 must be [B, H]")
+    T = _box_targets(labels, boxes, lens, B, "box_train_forward")
+    need = box_train_ws_floats(B, T, H, L, K, A)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=_F32, device=h0.device)
+    _chk(ws)
+    trace = torch.empty((B, T, L + 12 * K), dtype=_F32, device=h0.device)
+    x0, y0, w0, r0 = (float(v) for v in first_input)
+    _lib.call("objgan_box_train_forward", _p(h0), _p(c0), _p(labels), _p(boxes), _p(lens), *[_p(w) for w in weights],
+              x0, y0, w0, r0, _p(trace), _p(ws), ws.numel(), B, T, H, L, K, A,
+              box_decode_cpw() if cpw is None else int(cpw), _stream())
+    return trace, ws
+
+
+def box_train_loss(trace, labels, boxes, lens, weight, lamda1, lamda2, K, pad=0):
+    """The reference's Perplexity and BBLoss over a trace.  -> sums [4B + 1] float64 on the device (per caption: label
+    term, box term, non-pad steps, arg-max matches; the last entry is sum_b n_b) and dtrace, the gradient of
+    (lamda1 sum label + lamda2 sum box) / sum n with respect to the trace."""
+    _chk(trace, weight)
+    trace, weight = _c(trace), _c(weight)
+    B = trace.shape[0]
+    T = _box_targets(labels, boxes, lens, B, "box_train_loss")
+    L = weight.numel()
+    if trace.dim() != 3 or trace.shape[1] != T or trace.shape[2] != L + 12 * K:
+        raise _lib.ObjganHipError("box_train_loss: trace must be [B, T, L + 12K]")
+    sums = torch.zeros(4 * B + 1, dtype=torch.float64, device=trace.device)
+    dtrace = torch.empty_like(trace)
+    _lib.call("objgan_box_train_loss", _p(trace), _p(labels), _p(boxes), _p(lens), _p(weight), float(lamda1),
+              float(lamda2), _p(sums), _p(dtrace), B, T, L, int(K), int(pad), _stream())
+    return sums, dtrace
+
+
+def box_train_backward(dtrace, trace, c0, labels, lens, weights, ws, grads=None, cpw=None):
+    """BPTT from dtrace to the gradients of the 17 tensors (kernel layout).  `grads`: 17 views to write into (of a
+    box_arena); a new arena otherwise.  Every element is written; two runs give the same bits."""
+    _chk(dtrace, trace, c0, ws, *weights)
+    H, L, K, A = _box_train_dims(weights, "box_train_backward")
+    dtrace, trace, c0 = _c(dtrace), _c(trace), _c(c0)
+    B, T = trace.shape[0], trace.shape[1]
+    if tuple(dtrace.shape) != tuple(trace.shape) or trace.shape[2] != L + 12 * K or tuple(c0.shape) != (B, H) or \
+            tuple(labels.shape) != (B, T + 1) or labels.dtype != torch.int32 or not labels.is_cuda or \
+            tuple(lens.shape) != (B,) or lens.dtype != torch.int32 or not lens.is_cuda:
+        raise _lib.ObjganHipError("box_train_backward: inconsistent shapes")
+    if grads is None:
+        grads = box_arena(box_weight_shapes(H, L, K, A), trace.device)[1]
+    _chk(*grads)
+    if [tuple(g.shape) for g in grads] != box_weight_shapes(H, L, K, A) or any(not g.is_contiguous() for g in grads):
+        raise _lib.ObjganHipError("box_train_backward: 17 contiguous gradient tensors in the kernel's layout expected")
+    ptrs = (ctypes.c_void_p * 17)(*[g.data_ptr() for g in grads])
+    _lib.call("objgan_box_train_backward", _p(dtrace), _p(trace), _p(c0), _p(_c(labels)), _p(_c(lens)),
+              _p(weights[7]), _p(weights[8]), _p(weights[11]), _p(weights[13]), _p(weights[15]), ptrs, _p(ws),
+              ws.numel(), B, T, H, L, K, A, box_decode_cpw() if cpw is None else int(cpw), _stream())
+    return grads
+
+
+def box_train_clip(flat_grads, max_norm, partials=None, out=None):
+    """-> out (2 floats on the device): max(1, (norm + 1e-6) / max_norm), the divisor clip_grad_norm_ applies, and the
+    global L2 norm of the flat gradient arena.  No host read."""
+    _chk(flat_grads, out)
+    if partials is None:
+        partials = torch.empty(256, dtype=torch.float64, device=flat_grads.device)
+    if out is None:
+        out = torch.empty(2, dtype=_F32, device=flat_grads.device)
+    if not partials.is_cuda or partials.dtype != torch.float64 or partials.numel() < 256 or out.numel() < 2:
+        raise _lib.ObjganHipError("box_train_clip: partials is >= 256 float64, out 2 floats, on the GPU")
+    _lib.call("objgan_box_train_clip", _p(_c(flat_grads)), flat_grads.numel(), float(max_norm), _p(partials), _p(out),
+              _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # optimiser on flat arenas
 # ----------------------------------------------------------------------------------------------
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, n=None):

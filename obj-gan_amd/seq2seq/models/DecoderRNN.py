@@ -19,6 +19,30 @@ def draw_noise(rng, n, steps):
     return noise
 
 
+_TRANSPOSED = (7, 8, 11, 13, 15)
+
+
+class _TeacherForced(torch.autograd.Function):
+    """trace = objgan_box_train_forward(...); backward = objgan_box_train_backward, gradients handed back in the nn
+    layout.  The transposed copies the kernels stream are made per call here (the autograd route serves a trainer loop
+    kept from the reference; the fused step keeps its master copy in the kernel's layout instead)."""
+
+    @staticmethod
+    def forward(ctx, h0, c0, labels, boxes, lens, first, *params):
+        with torch.no_grad():
+            W = [(p.t() if i in _TRANSPOSED else p).detach().contiguous() for i, p in enumerate(params)]
+        trace, ws = ops.box_train_forward(h0, c0, labels, boxes, lens, W, first)
+        ctx.saved = (trace, ws, c0, labels, lens, W)
+        return trace
+
+    @staticmethod
+    def backward(ctx, dtrace):
+        trace, ws, c0, labels, lens, W = ctx.saved
+        grads = ops.box_train_backward(dtrace.contiguous(), trace, c0, labels, lens, W, ws)
+        out = [(g.t() if i in _TRANSPOSED else g) for i, g in enumerate(grads)]
+        return (None,) * 6 + tuple(out)
+
+
 class DecoderRNN(nn.Module):
     """The box generator's decoder, sampling path (reference box_generation/seq2seq/models/DecoderRNN.py): same
     constructor arguments and the same 17 state-dict tensors (`l_embedding.weight`, `xy_embedding.*`, `wh_embedding.*`,
@@ -31,7 +55,14 @@ class DecoderRNN(nn.Module):
     point is the Cholesky factor of the reference's covariance applied to two normals (numpy's multivariate_normal
     factors the same matrix by SVD: same law, other sample for the same normals).
 
-    Training (is_training=1) and the attention variant are not built here."""
+    Training: forward(..., target_*_variables, is_training=1) is the teacher-forced pass of B captions in ONE launch of
+    objgan_box_train_forward, connected to autograd by _TeacherForced (its backward is objgan_box_train_backward), so
+    the reference's loop of loss calls and loss.backward() works on the returned lists for one caption or a batch of
+    equal lengths (rows past a caption's length are zero, where the reference's BBLoss divides 0 by 0: for captions of
+    unequal lengths use SupervisedTrainer, whose fused step masks by length).  The fused step of
+    seq2seq.trainer does not go through autograd.  input_dropout_p must be 0; dropout_p is accepted and does nothing,
+    as in torch (nn.LSTM applies dropout between layers only, and there is one layer).  Free-running training
+    (is_training=1 without targets) and the attention variant are not built here."""
     KEY_ATTN_SCORE = 'attention_score'
     KEY_LENGTH = 'length'
     KEY_SEQUENCE = 'sequence'
@@ -91,6 +122,48 @@ class DecoderRNN(nn.Module):
             self._packed = (key, packed)
         return self._packed[1]
 
+    def _params(self):
+        """the 17 parameters in the kernel's order (nn layout)"""
+        return (self.l_embedding.weight, self.xy_embedding.weight, self.xy_embedding.bias,
+                self.wh_embedding.weight, self.wh_embedding.bias,
+                self.next_xy_embedding.weight, self.next_xy_embedding.bias,
+                self.rnn.weight_ih_l0, self.rnn.weight_hh_l0, self.rnn.bias_ih_l0, self.rnn.bias_hh_l0,
+                self.l_out.weight, self.l_out.bias, self.xy_out.weight, self.xy_out.bias,
+                self.wh_out.weight, self.wh_out.bias)
+
+    @staticmethod
+    def pack_targets(target_l, target_x, target_y, target_w, target_h, pad=0):
+        """[B, T + 1] targets -> labels int32, boxes [B, T + 1, 4] fp32, lens [B] int32 (steps up to the last non-pad
+        label) on the targets' device, without a host read"""
+        labels = target_l.to(torch.int32).contiguous()
+        boxes = torch.stack((target_x, target_y, target_w, target_h), dim=2).to(torch.float32).contiguous()
+        T = labels.shape[1] - 1
+        steps = torch.arange(1, T + 1, device=labels.device, dtype=torch.int32)
+        lens = ((labels[:, 1:] != pad).to(torch.int32) * steps).amax(dim=1).to(torch.int32).contiguous()
+        return labels, boxes, lens
+
+    def _forward_train(self, encoder_hidden, target_l, target_x, target_y, target_w, target_h):
+        if self.input_dropout_p != 0:
+            raise NotImplementedError("input_dropout_p != 0: the training kernels apply no input dropout (the "
+                                      "reference's sample.py never sets it)")
+        if encoder_hidden is None:
+            raise ValueError("the training path needs the encoder's (h_n, c_n)")
+        h0, c0 = (s[0] for s in self._init_state(encoder_hidden))
+        labels, boxes, lens = self.pack_targets(target_l, target_x, target_y, target_w, target_h)
+        T = labels.shape[1] - 1
+        first = (self.x_mean, self.y_mean, self.w_mean, self.r_mean)
+        trace = _TeacherForced.apply(h0.detach(), c0.detach(), labels, boxes, lens, first, *self._params())
+        L, K = self.l_output_size, self.gmm_comp_num
+        Q = K * self.gmm_param_num
+        l_outputs = [trace[:, t, :L] for t in range(T)]
+        xy = [tuple(trace[:, t, L + i * K:L + (i + 1) * K] for i in range(6)) for t in range(T)]
+        wh = [tuple(trace[:, t, L + Q + i * K:L + Q + (i + 1) * K] for i in range(6)) for t in range(T)]
+        sequence = [o.detach().topk(1)[1].squeeze(1) for o in l_outputs]
+        # 'length': the decode steps of each caption's targets (one host read; this route is not the fused one)
+        ret_dict = {DecoderRNN.KEY_SEQUENCE: sequence, DecoderRNN.KEY_LENGTH: lens.tolist(),
+                    DecoderRNN.KEY_XYS: [], DecoderRNN.KEY_WHS: []}
+        return l_outputs, xy, wh, None, ret_dict
+
     def _init_state(self, encoder_hidden):
         return tuple(self._cat_directions(h) for h in encoder_hidden)
 
@@ -108,8 +181,11 @@ class DecoderRNN(nn.Module):
         final state never (None).  ret_dict holds, per caption, 'sequence' (label indices, the <eos> step included),
         'length' (steps taken), 'xy' and 'wh' (lists of float64 pairs)."""
         if is_training:
-            raise NotImplementedError("is_training=1: training the box generator is out of scope here; layouts are "
-                                      "sampled from a checkpoint the reference trained")
+            if target_l_variables is None or target_x_variables is None:
+                raise NotImplementedError("is_training=1 without targets: free-running training of the box generator "
+                                          "is out of scope here; pass the target sequences (teacher forcing)")
+            return self._forward_train(encoder_hidden, target_l_variables, target_x_variables, target_y_variables,
+                                       target_w_variables, target_h_variables)
         if encoder_hidden is None or early_stop_len is None:
             raise ValueError("the sampling path needs the encoder's (h_n, c_n) and early_stop_len")
         h0, c0 = (s[0] for s in self._init_state(encoder_hidden))
