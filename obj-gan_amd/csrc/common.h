@@ -48,6 +48,24 @@ static inline int og_stream_grid(long work_items, int block) {
     return (int)g;
 }
 
+// Sum of the 16-byte groups p[0], p[stride4], .. p[(splits - 1) * stride4] of a split workspace, every lane of the group
+// in slot order starting from slot 0's value (the bits of the serial `v += p[k * stride]` chain), U loads in flight.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <int U>
+__device__ __forceinline__ f32x4 og_sum_slots4(const f32x4* __restrict__ p, int splits, size_t stride4) {
+    f32x4 v = p[0];
+    int k = 1;
+    for (; k + U <= splits; k += U) {
+        f32x4 t[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) t[u] = p[(size_t)(k + u) * stride4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v += t[u];
+    }
+    for (; k < splits; ++k) v += p[(size_t)k * stride4];
+    return v;
+}
+
 __device__ __forceinline__ float og_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

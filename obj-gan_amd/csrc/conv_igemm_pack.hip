@@ -212,13 +212,54 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const PackArg
 // ymax (may be null; zeroed by the caller): the partial maxima of |out| for an fp16x2 consumer, added with one integer
 // atomicMax per workgroup -- round 6: this was a separate pass over the output behind every split launch with a fused
 // ReLU / LeakyReLU (the Inception chain's small maps).
+// V4 (the host asks for it when ws + seg_off is 16-byte aligned, ws_stride % 4 == 0 and total < 2^31): four consecutive
+// elements per thread as one 16-byte load per slot, eight slots in flight (a one-workgroup launch behind a long-K head is
+// as long as the latency of its chain of slot loads), every lane summed in the same slot order, one 16-byte store where
+// out allows it.  The bias channel (e / HW) % M is derived once per group in 32-bit arithmetic and stepped with a carry
+// where a group straddles channels (HW = 289, 25, 1 225).  The scalar loop behind it takes the total % 4 tail, or
+// everything.
+template <bool V4>
 __global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __restrict__ ws, int splits, long ws_stride,
                                                              long seg_off, float* __restrict__ out, long total,
                                                              const float* __restrict__ bias, int M, int HW, int act,
                                                              float* __restrict__ ymax) {
     __shared__ float red[4];
     float vmax = 0.f;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    long e0 = 0;
+    if (V4) {
+        const unsigned n4 = (unsigned)(total >> 2), uHW = (unsigned)HW, uM = (unsigned)M;
+        const f32x4* p4 = reinterpret_cast<const f32x4*>(ws + seg_off);
+        const size_t stride4 = (size_t)ws_stride >> 2;
+        const bool one_channel = (HW & 3) == 0;
+        for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < n4; g += gridDim.x * 256u) {
+            f32x4 v = og_sum_slots4<8>(p4 + g, splits, stride4);
+            if (bias) {
+                const unsigned q = (g * 4u) / uHW;
+                unsigned rem = g * 4u - q * uHW, ch = q % uM;
+                if (one_channel) {
+                    v += bias[ch];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        v[j] += bias[ch];
+                        if (++rem == uHW) { rem = 0; ch = ch + 1 == uM ? 0 : ch + 1; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = og_act(v[j], act);
+            float* o = out + ((size_t)g << 2);
+            if (!((size_t)o & 15)) {
+                *reinterpret_cast<f32x4*>(o) = v;
+            } else {                                   // (an output view that starts off a 16-byte boundary)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = v[j];
+            }
+            vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        }
+        e0 = (long)n4 << 2;
+    }
+    for (long e = e0 + (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const float* p = ws + seg_off + e;
         float v = p[0];
         for (int k = 1; k < splits; ++k) v += p[(size_t)k * ws_stride];
@@ -231,8 +272,13 @@ __global__ __launch_bounds__(256) void splitk_combine_kernel(const float* __rest
 }
 void og_launch_splitk_combine(const float* ws, int splits, long ws_stride, long seg_off, float* out, long total,
                               const float* bias, int M, int HW, int act, float* ymax, hipStream_t s) {
-    hipLaunchKernelGGL(splitk_combine_kernel, dim3(og_stream_grid(total, 256)), dim3(256), 0, s, ws, splits, ws_stride, seg_off,
-                       out, total, bias, M, HW, act, ymax);
+    const bool v4 = !((size_t)(ws + seg_off) & 15) && !(ws_stride & 3) && total >= 4 && total < (1L << 31);
+    if (v4)
+        hipLaunchKernelGGL(splitk_combine_kernel<true>, dim3(og_stream_grid((total + 3) >> 2, 256)), dim3(256), 0, s, ws, splits,
+                           ws_stride, seg_off, out, total, bias, M, HW, act, ymax);
+    else
+        hipLaunchKernelGGL(splitk_combine_kernel<false>, dim3(og_stream_grid(total, 256)), dim3(256), 0, s, ws, splits,
+                           ws_stride, seg_off, out, total, bias, M, HW, act, ymax);
 }
 
 // fp32 -> bf16 (RNE), same layout: the dy operand of conv_wgrad_bfb_kernel.  n4 = elements / 4.

@@ -17,42 +17,40 @@
 // 986-1048, 1184-1312, which the reference hands to cuDNN.
 #include "conv_igemm_host.h"
 
-// fp32 [N][C][HW] -> records [N][Cp/16][2][HW][16]; 64 channels x 64 pixels per workgroup through LDS
-// (256-byte rows in, 1 KiB runs per wave and piece out).
+// fp32 [N][C][HW] -> records [N][Cp/16][2][HW][16], no LDS: a thread owns one pixel of one 16-channel chunk (grid: pixel
+// blocks, chunks, images).  Its 16 channel loads are dwords coalesced along the pixels of the wave; the 16 channels of a
+// pixel ARE one 32-byte record row per piece, written as two 16-byte stores -- a wave writes 2 KiB of contiguous memory
+// per piece.  Channels >= C read as 0 (the load goes to the chunk's first channel instead), pixels >= HW are not written.
+// (Four consecutive pixels per thread as 16-byte loads measured slower on every large tensor, 3.2 against 5.2 TB/s:
+// profiles/stream_passes.md.)
 __global__ __launch_bounds__(256) void h2_records_kernel(const float* __restrict__ x, const float* __restrict__ xmax,
                                                          _Float16* __restrict__ out, int C, int HW, int Cp) {
-    __shared__ float tile[64][65];
     og_fp16_saturate();
     const float xs = og_pow2(og_h2_exponent(xmax, threadIdx.x & 63));
-    const int n = blockIdx.z;
-    const int p0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const float* xn = x + (size_t)n * C * HW;
-#pragma unroll 4
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int c = c0 + cc, p = p0 + tx;
-        tile[cc][tx] = (c < C && p < HW) ? xn[(size_t)c * HW + p] : 0.f;
+    const int n = blockIdx.z, chunk = blockIdx.y, c0 = chunk * 16;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= HW) return;
+    const float* xp = x + ((size_t)n * C + c0) * HW + p;
+    float v[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        const bool ok = c0 + c < C;
+        const float t = xp[ok ? (size_t)c * HW : 0];
+        v[c] = ok ? t : 0.f;
     }
-    __syncthreads();
-    const int cg = threadIdx.x >> 5;                   // 8 channels = one 16-byte store per piece
-    if (c0 + cg * 8 >= Cp) return;
-    const int chunk = (c0 + cg * 8) >> 4, half = cg & 1;
-    _Float16* oh = out + ((size_t)n * (Cp / 16) + chunk) * 2 * (size_t)HW * 16 + half * 8;
+    _Float16* oh = out + (((size_t)n * (Cp / 16) + chunk) * 2 * (size_t)HW + p) * 16;
     _Float16* ol = oh + (size_t)HW * 16;
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int pp = (threadIdx.x & 31) + 32 * it;
-        const int p = p0 + pp;
-        if (p >= HW) continue;
+    for (int half = 0; half < 2; ++half) {
         f16x8 h, l;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float sv = tile[cg * 8 + j][pp] * xs;
+            const float sv = v[half * 8 + j] * xs;
             h[j] = (_Float16)sv;
             l[j] = (_Float16)og_sub(sv, (float)h[j]);
         }
-        *reinterpret_cast<f16x8*>(oh + (size_t)p * 16) = h;
-        *reinterpret_cast<f16x8*>(ol + (size_t)p * 16) = l;
+        *reinterpret_cast<f16x8*>(oh + half * 8) = h;
+        *reinterpret_cast<f16x8*>(ol + half * 8) = l;
     }
 }
 
@@ -673,9 +671,11 @@ int objgan_h2_records(const float* x, const float* xmax, void* rec, int N, int C
     if (N <= 0 || C <= 0 || HW <= 0) return OG_OK;
     const int Cp = (C + 15) / 16 * 16;
     if ((double)N * Cp * (double)HW * 4.0 >= 4.0e9 || N > 65535) return OG_BAD_ARGS;
-    // (round 6 tried 64 x 128 tiles fetched as 16-byte pieces: 7.8 ms per step against 7.0 for this form in the same profile
-    //  -- the larger LDS tile halves the workgroups per CU; rejected, profiles/r06_ab_variants.txt)
-    hipLaunchKernelGGL(h2_records_kernel, dim3(og_cdiv(HW, 64), og_cdiv(Cp, 64), N), dim3(256), 0, (hipStream_t)stream,
+    // (round 6 tried 64 x 128 LDS tiles fetched as 16-byte pieces: slower than 64 x 64 -- the larger tile halves the
+    //  workgroups per CU, profiles/r06_ab_variants.txt; the form without LDS replaced both)
+    int block = 256;                                    // no wave without a pixel
+    while (block > 64 && (HW + block - 1) / block * block - HW >= 64) block >>= 1;
+    hipLaunchKernelGGL(h2_records_kernel, dim3(og_cdiv(HW, block), Cp / 16, N), dim3(block), 0, (hipStream_t)stream,
                        x, xmax, reinterpret_cast<_Float16*>(rec), C, (int)HW, Cp);
     return og_launch_status();
 }

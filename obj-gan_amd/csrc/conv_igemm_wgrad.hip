@@ -18,10 +18,44 @@
 
 // dw rows <- sum over the splits of a weight-gradient launch (WgradArgs::ws): local row r of the slot is dw row
 // m_begin + r for r < main_rows, extra row xr_begin + (r - main_rows) behind them.
+// V4 (the host asks for it when ws is 16-byte aligned, ws_stride % 4 == 0 and total < 2^31): four consecutive elements per
+// thread as one 16-byte load per slot, several slots in flight, every lane summed in the same slot order.  No division:
+// the slot is two runs of consecutive dw elements -- the main rows from dw row m_begin, the extra rows from dw row
+// xr_begin -- so an element's address is its index plus the offset of its run.  A group that lies in one run at a
+// 16-byte aligned address is one 16-byte store (every group when ncol % 4 == 0 and dw is aligned; every main-row group
+// of the 194-channel layers, ncol = 1 746, whose launches start at row 0); any other group stores its four elements one
+// by one.  The scalar loop behind it takes the total % 4 tail, or everything.
+template <bool V4>
 __global__ __launch_bounds__(256) void wgrad_combine_kernel(const float* __restrict__ ws, int splits, long ws_stride,
                                                             float* __restrict__ dw, int ncol, int m_begin, int main_rows,
                                                             int xr_begin, long total, int accumulate) {
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    long e0 = 0;
+    if (V4) {
+        const unsigned n4 = (unsigned)(total >> 2);
+        const f32x4* p4 = reinterpret_cast<const f32x4*>(ws);
+        const size_t stride4 = (size_t)ws_stride >> 2;
+        const long main_end = (long)main_rows * ncol;                         // slot elements of the main rows
+        // element e of the slot is dw[off_main + e], or dw[off_xr + e] from main_end on -- offsets, not pointers: a launch
+        // without extra rows has no element from main_end on, and whatever xr_begin holds then never becomes an address
+        const long off_main = (long)m_begin * ncol, off_xr = (long)xr_begin * ncol - main_end;
+        for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < n4; g += gridDim.x * 256u) {
+            const f32x4 v = og_sum_slots4<8>(p4 + g, splits, stride4);
+            const long e = (long)g << 2;
+            float* o = dw + ((e < main_end ? off_main : off_xr) + e);
+            if ((e + 3 < main_end || e >= main_end) && !((size_t)o & 15)) {
+                f32x4* o4 = reinterpret_cast<f32x4*>(o);
+                *o4 = accumulate ? *o4 + v : v;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float* oj = dw + ((e + j < main_end ? off_main : off_xr) + e + j);
+                    *oj = accumulate ? *oj + v[j] : v[j];
+                }
+            }
+        }
+        e0 = (long)n4 << 2;
+    }
+    for (long e = e0 + (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const float* p = ws + e;
         float v = p[0];
         for (int k = 1; k < splits; ++k) v += p[(size_t)k * ws_stride];
@@ -1022,8 +1056,13 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_bfb_kernel(const WgradArgs
 
 int og_launch_wgrad_combine(const WgradArgs& a, int splits, hipStream_t s) {
     const long slot = a.ws_stride;
-    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(og_stream_grid(slot, 256)), dim3(256), 0, s, a.ws, splits, slot,
-                       a.dw, a.ncol, a.m_begin, a.m_end - a.m_begin, a.xr_begin, slot, a.accumulate);
+    const bool v4 = !((size_t)a.ws & 15) && !(slot & 3) && slot >= 4 && slot < (1L << 31);
+    if (v4)
+        hipLaunchKernelGGL(wgrad_combine_kernel<true>, dim3(og_stream_grid(slot >> 2, 256)), dim3(256), 0, s, a.ws, splits,
+                           slot, a.dw, a.ncol, a.m_begin, a.m_end - a.m_begin, a.xr_begin, slot, a.accumulate);
+    else
+        hipLaunchKernelGGL(wgrad_combine_kernel<false>, dim3(og_stream_grid(slot, 256)), dim3(256), 0, s, a.ws, splits,
+                           slot, a.dw, a.ncol, a.m_begin, a.m_end - a.m_begin, a.xr_begin, slot, a.accumulate);
     return og_launch_status();
 }
 

@@ -610,20 +610,47 @@ __global__ void norm_affine_grad_kernel(const float* __restrict__ bsums, float* 
 
 // ---- plain activations on conv outputs (forward is fused in the conv epilogue) ----------
 // kind 1: LeakyReLU(0.2) from the OUTPUT y (sign(y) == sign(z));  2: tanh;  3: sigmoid;  4: ReLU
+__device__ __forceinline__ float act_bwd_one(float d, float o, int kind) {
+    float r;
+    if (kind == 1) r = d * (o > 0.f ? 1.f : 0.2f);
+    else if (kind == 2) r = d * (1.f - o * o);
+    else if (kind == 3) r = d * o * (1.f - o);
+    else r = o > 0.f ? d : 0.f;
+    return r;
+}
+// V4 (the host asks for it when dy, y and dz are 16-byte aligned): four elements per thread as 16-byte loads and one
+// 16-byte store, two groups per trip so that four loads are in flight; the scalar loop behind it takes the total % 4
+// tail, or everything.
+template <bool V4>
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ dy,
                                                       const float* __restrict__ y,
                                                       float* __restrict__ dz, long total, int kind,
                                                       float* __restrict__ amax) {
     __shared__ float amax_red[4];
     float vmax = 0.f;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+    long e0 = 0;
+    if (V4) {
+        const long n4 = total >> 2, step = (long)gridDim.x * 256;
+        const float4* d4 = reinterpret_cast<const float4*>(dy);
+        const float4* y4 = reinterpret_cast<const float4*>(y);
+        float4* z4 = reinterpret_cast<float4*>(dz);
+        for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < n4; g += 2 * step) {
+            const long g1 = g + step < n4 ? g + step : g;          // (the last trip of a thread may hold one group: twice)
+            const float4 da = d4[g], oa = y4[g], db = d4[g1], ob = y4[g1];
+            const float ra[4] = {act_bwd_one(da.x, oa.x, kind), act_bwd_one(da.y, oa.y, kind),
+                                 act_bwd_one(da.z, oa.z, kind), act_bwd_one(da.w, oa.w, kind)};
+            const float rb[4] = {act_bwd_one(db.x, ob.x, kind), act_bwd_one(db.y, ob.y, kind),
+                                 act_bwd_one(db.z, ob.z, kind), act_bwd_one(db.w, ob.w, kind)};
+            z4[g] = make_float4(ra[0], ra[1], ra[2], ra[3]);
+            if (g1 != g) z4[g1] = make_float4(rb[0], rb[1], rb[2], rb[3]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) vmax = fmaxf(vmax, fmaxf(fabsf(ra[j]), fabsf(rb[j])));
+        }
+        e0 = n4 << 2;
+    }
+    for (long e = e0 + (long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (long)gridDim.x * blockDim.x) {
-        const float o = y[e], d = dy[e];
-        float r;
-        if (kind == 1) r = d * (o > 0.f ? 1.f : 0.2f);
-        else if (kind == 2) r = d * (1.f - o * o);
-        else if (kind == 3) r = d * o * (1.f - o);
-        else r = o > 0.f ? d : 0.f;
+        const float r = act_bwd_one(dy[e], y[e], kind);
         dz[e] = r;
         vmax = fmaxf(vmax, fabsf(r));
     }
@@ -853,9 +880,11 @@ int objgan_act_backward(const float* dy, const float* y, float* dz, long total, 
     OG_ENTRY();
     if (kind < 1 || kind > 4) return OG_BAD_ARGS;
     if (total <= 0) return OG_OK;
-    int grid = og_stream_grid(total, 256);
+    const bool v4 = !(((size_t)dy | (size_t)y | (size_t)dz) & 15) && total >= 4;
+    int grid = og_stream_grid(v4 ? (total + 3) >> 2 : total, 256);
     if (amax && grid > OG_AMAX_SLOTS) grid = OG_AMAX_SLOTS;      // every workgroup owns a slot
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, y, dz, total, kind, amax);
+    if (v4) hipLaunchKernelGGL(act_bwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, y, dz, total, kind, amax);
+    else hipLaunchKernelGGL(act_bwd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, y, dz, total, kind, amax);
     return og_launch_status();
 }
 
