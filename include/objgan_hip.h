@@ -38,7 +38,10 @@ extern "C" {
 
 /* ---- ROIAlign (reference models/roi_align/src/roi_align_kernel.cu:15-143) ------------------ */
 /* features [B, C, H, W], rois [num_rois, roi_cols = 5] = (batch_idx, x1, y1, x2, y2),
- * output [num_rois, C, aligned_height, aligned_width].  Returns 0 if roi_cols != 5. */
+ * output [num_rois, C, aligned_height, aligned_width].  Returns 0 if roi_cols != 5.
+ * All three ROIAlign entry points refuse a map with height < 2 or width < 2 (as they refuse aligned_height < 2 or
+ * aligned_width < 2), before any launch: the reference's kernels index row height - 2 / column width - 2
+ * (hstart = min(floor(h), height - 2) = -1 for a valid sample) and read before the tensor there. */
 int objgan_roi_align_forward(const float* features, const float* rois, float* output,
                              int num_rois, int roi_cols, int channels, int height, int width,
                              int aligned_height, int aligned_width, float spatial_scale,

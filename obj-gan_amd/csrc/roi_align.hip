@@ -427,6 +427,7 @@ int objgan_roi_align_forward(const float* features, const float* rois, float* ou
     if (roi_cols != 5) return OG_BAD_ARGS;                       // roi_align_cuda.c:18-22
     if (aligned_height * aligned_width > ROI_MAX_SAMPLES || aligned_height < 2 || aligned_width < 2)
         return OG_BAD_ARGS;
+    if (height < 2 || width < 2) return OG_BAD_ARGS;             // hstart = min(floor(h), height - 2) = -1: a read before the map
     if (num_rois <= 0 || channels <= 0) return OG_OK;
     const int S = aligned_height * aligned_width;
     const int cpb = roi_c_per_block(channels, S);
@@ -446,6 +447,7 @@ int objgan_roi_align_backward(const float* top_grad, const float* rois, float* b
     if (roi_cols != 5) return OG_BAD_ARGS;
     if (aligned_height * aligned_width > ROI_MAX_SAMPLES || aligned_height < 2 || aligned_width < 2)
         return OG_BAD_ARGS;
+    if (height < 2 || width < 2) return OG_BAD_ARGS;             // hstart = min(floor(h), height - 2) = -1: a read before the map
     if (num_rois <= 0 || channels <= 0) return OG_OK;
     const int S = aligned_height * aligned_width;
     const int cpb = roi_c_per_block(channels, S);
@@ -482,6 +484,7 @@ int objgan_roi_align_backward_ordered(const float* top_grad, const float* rois, 
     if (roi_cols != 5) return OG_BAD_ARGS;
     if (aligned_height * aligned_width > ROI_MAX_SAMPLES || aligned_height < 2 || aligned_width < 2)
         return OG_BAD_ARGS;
+    if (height < 2 || width < 2) return OG_BAD_ARGS;             // hstart = min(floor(h), height - 2) = -1: a read before the map
     if (num_rois <= 0 || channels <= 0) return OG_OK;
     const long need = objgan_roi_align_backward_ws_floats(batch_size, num_rois, channels, height, width,
                                                           aligned_height, aligned_width);

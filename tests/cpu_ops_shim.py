@@ -102,6 +102,21 @@ def lift_stem_conv(seg, w, bias, size):
     return F.conv2d(F.pad(up, (1, 1, 1, 1), mode="reflect"), w, bias)
 
 
+class _LiftTapsFn(object):
+    """definition of ops._LiftTapsFn: z [N, 9 Mo, h, w] holds, in channel (dh * 3 + dw) * Mo + co, tap (dh, dw) of output
+    channel co at the source resolution; y = bias + the sum over the nine taps of the (dh, dw) window of
+    reflect_pad(lift(z_tap))"""
+
+    @staticmethod
+    def apply(z, bias, SH, SW):
+        Mo = z.shape[1] // 9
+        y = torch.zeros((z.shape[0], Mo, SH, SW), dtype=torch.float32)
+        for t in range(9):
+            up = F.interpolate(z[:, t * Mo:(t + 1) * Mo].float(), size=(SH, SW), mode="bilinear", align_corners=True)
+            y = y + F.pad(up, (1, 1, 1, 1), mode="reflect")[:, :, t // 3:t // 3 + SH, t % 3:t % 3 + SW]
+        return y if bias is None else y + bias.view(1, -1, 1, 1)
+
+
 def bmm(A, B):
     return torch.bmm(A, B)
 

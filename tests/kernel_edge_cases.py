@@ -1,5 +1,5 @@
-"""Edge-shape cases of the norm, attention, pooling, resize, optimiser and LSTM kernels, with their fp64 references, shared
-by tests/test_kernel_edges_cpu.py and tests/test_kernel_edges_gpu.py (no GPU import here).
+"""Edge-shape cases of the norm, attention, pooling, resize, optimiser, LSTM, ROIAlign and lift-stem kernels, with their
+fp64 references, shared by tests/test_kernel_edges_cpu.py and tests/test_kernel_edges_gpu.py (no GPU import here).
 
 One table per operator; every entry carries an `id` that names the branch of the host dispatch / the kernel it is there
 for.  One `run_<operator>(ns, case, dtype, device)` per operator builds the seeded fp32 inputs of a case, casts them to
@@ -7,7 +7,7 @@ for.  One `run_<operator>(ns, case, dtype, device)` per operator builds the seed
 runner serves three purposes:
 
     reference(op, case)   ns = REF (the plain definitions below) in float64 on the CPU
-    oracle32(op, case)    ns = REF in float32 on the CPU (what the existing suite compares with)
+    oracle32(op, case)    ns = REF in float32 on the CPU (what the existing suite compares with; ROIAlign: the C oracle)
     the kernels           ns = objgan_hip.ops in float32 on the device (or tests/cpu_ops_shim.py on the CPU)
 
 Metric per compared tensor (`max_err`): max |a - ref64| / max |ref64| (denominator 1 for an all-zero reference): a
@@ -17,6 +17,7 @@ e_k <= M[family] * max(e_o, 2^-23) with e_o the same figure of the fp32 oracle, 
 import math
 import zlib
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -51,6 +52,9 @@ M = {
     "fold": 4.0,             # 0.52   sum2x2-17x5
     "stream": 4.0,           # 1.00   adam-n600001-second-grid-stride-trip
     "lstm": 8.0,             # 1.21   max_len3-shorter-than-captions
+    "roi": 8.0,              # 1.98   unstaged-many-taps (dfeat of the atomic scatter, 1.72 in another run; the ordered backward: 1.25, C64)
+    "lift_taps": 8.0,        # 1.42   identity-5-to-5
+    "lift_stem": 8.0,        # 1.07   1x3-to-4-h1
 }
 
 # Per-tensor exceptions to M: running_var of the norm family, for the reason above; the family's M then comes from
@@ -75,6 +79,8 @@ def m_bound(fam, name):
 #   bilinear      1e-5                                                                test_bilinear_resize
 #   stream        p, m, v, avg 1e-6                                                   test_adam_and_ema, test_gated_adam_*
 #   lstm          1e-5                                                                test_rnn_encoder_matches_oracle_*
+#   roi           dfeat 1e-5 (y is bit-equal to the C oracle besides)                 test_roi_align_bit_exact
+#   lift_stem     1e-4 (TOL), and the same for the four lift kernels alone            test_lift_stem_conv_matches_the_reference_formulation
 # Tensors without an existing test:
 #   norm_eval y   1e-4, the bound of the training-mode forward (the same apply arithmetic).
 #   fold y        1e-6, as the average pools: a sum of four fp32 terms (sum2x2) or at most four (reflect_fold), each
@@ -95,6 +101,9 @@ RL2 = {
     "fold": {"y": 1e-6},
     "stream": {"p": 1e-6, "m": 1e-6, "v": 1e-6, "avg": 1e-6, "update": 1e-4},
     "lstm": {"words": 1e-5, "sent": 1e-5},
+    "roi": {"y": 1e-5, "dfeat": 1e-5},
+    "lift_taps": {"y": 1e-4, "dz": 1e-4, "dbias": 1e-4},
+    "lift_stem": {"y": 1e-4, "dseg": 1e-4, "dw": 1e-4, "db": 1e-4},
 }
 ATTN_DSRC_MULTI_CHUNK = 5e-4
 
@@ -109,6 +118,10 @@ def rl2_bound(fam, case, name):
         # for ANY fp32 implementation: below the 1e-5 of the existing test up to 83 pixels (its maps have at most 64),
         # 4.8e-5 on the 400-pixel map of the second-trip case (the fp32 oracle measures 3.1e-5 there).
         return max(RL2[fam][name], EPS32 * max(case["shape"][2], case["shape"][3]))
+    if fam in ("lift_taps", "lift_stem"):
+        # the same coordinate rule (the tables hold the fp32 source coordinates of bilinear_fwd_kernel): 8.7e-5 at the
+        # 726 pixels of the second-trip case, so 1e-4 stays in force for every case here
+        return max(RL2[fam][name], EPS32 * max(case["SH"], case["SW"]))
     return RL2[fam][name]
 
 
@@ -118,6 +131,19 @@ IN_FUSED_MAX = 65536         # csrc/norm.hip OG_IN_FUSED_MAX
 SM_ROWS_MAX = 1024           # csrc/attention.hip 64 * OG_SM_PER
 MM_RMAX = 16                 # csrc/attention.hip MM_RMAX
 STREAM_ITEMS = 2048 * 256    # csrc/common.h og_stream_grid: work items of one trip of a grid-stride loop
+ROI_MAX_SAMPLES = 256        # csrc/roi_align.hip: AH * AW a workgroup parks in LDS
+ROI_TAB_MAX = 512            # rois per call the ordered backward takes
+ROI_LDS_SMP = 1024           # samples of one image the gather kernel stages in LDS ...
+ROI_LDS_G = 4096             # ... with nlist * nc * S top gradients of the slab
+ROI_LDS_START = 4608         # anchor-range starts in LDS when HW + 1 <= this
+ROI_SEQ = 24                 # a (pixel, channel) element with at most this many taps is summed by one lane
+ROI_SUB = 16                 # lanes of the butterfly above it
+LIFT_MAXE = 8                # csrc/lift_stem.hip: CSR entries of one source index an adjoint thread keeps in registers
+
+
+def roi_cpb(channels):
+    """channels per workgroup of roi_align_bwd_gather_kernel (objgan_roi_align_backward_ordered)"""
+    return 8 if channels >= 64 else 1
 
 
 def _gen(case):
@@ -193,6 +219,32 @@ class _MaskedMaxFirst(torch.autograd.Function):
         hit = arg.unsqueeze(2) == torch.arange(R).view(1, 1, R, 1)
         df = (dout.reshape(B, num, 1, P) * m4 * hit).sum(dim=3)
         return df.reshape(ctx.fshape), None, None, None
+
+
+def roi_geometry_np(rois, H, W, AH, AW, scale):
+    """The sample geometry of ROIAlign in the arithmetic the header of csrc/roi_align.hip documents: roi quantities are
+    float; `end - start + 1.`, `size / (aligned - 1.)` are evaluated in double and rounded to float; h = ph * bin + start
+    is a float product, then a float sum; hstart = (int) fminf(floor(h), H - 2).  rois [n, 5] float32 with an integer
+    image index -> per (roi, sample = ph * AW + pw): off = hstart * W + wstart, valid, h_ratio, w_ratio (float32), and
+    image [n]."""
+    f32, f64 = np.float32, np.float64
+    r = np.asarray(rois, f32)
+    sc = f32(scale)
+    start_w, start_h, end_w, end_h = r[:, 1] * sc, r[:, 2] * sc, r[:, 3] * sc, r[:, 4] * sc
+    roi_w = np.maximum(((end_w - start_w).astype(f64) + 1.0).astype(f32), f32(0))
+    roi_h = np.maximum(((end_h - start_h).astype(f64) + 1.0).astype(f32), f32(0))
+    bin_h = (roi_h.astype(f64) / (f64(AH) - 1.0)).astype(f32)
+    bin_w = (roi_w.astype(f64) / (f64(AW) - 1.0)).astype(f32)
+    ph = np.repeat(np.arange(AH), AW).astype(f32)[None, :]
+    pw = np.tile(np.arange(AW), AH).astype(f32)[None, :]
+    h = (ph * bin_h[:, None]).astype(f32) + start_h[:, None]
+    w = (pw * bin_w[:, None]).astype(f32) + start_w[:, None]
+    assert h.dtype == f32 and w.dtype == f32
+    hstart = np.minimum(np.floor(h.astype(f64)).astype(f32), f32(H - 2)).astype(np.int64)
+    wstart = np.minimum(np.floor(w.astype(f64)).astype(f32), f32(W - 2)).astype(np.int64)
+    valid = ~((h < 0) | (h >= f32(H)) | (w < 0) | (w >= f32(W)))
+    return dict(off=hstart * W + wstart, hstart=hstart, wstart=wstart, valid=valid, h_ratio=h - hstart.astype(f32),
+                w_ratio=w - wstart.astype(f32), image=r[:, 0].astype(np.int64))
 
 
 def _group_count(x, per_channel):
@@ -316,6 +368,47 @@ class _Ref(object):
                 words[b, :, :t] = out[0, :t].t()
                 sent[b] = torch.cat([hn[0, 0], hn[1, 0]])
         return words, sent
+
+    @staticmethod
+    def roi_align(features, rois, aligned_height, aligned_width, spatial_scale):
+        """ROIAlign as csrc/roi_align.hip states it.  Which four pixels a sample reads (hstart, wstart), whether it
+        counts (valid) and its fractional offsets (h_ratio, w_ratio) are the operator's DEFINITION: an index decision,
+        taken once by roi_geometry_np in the float / double mix of the C reference.  Everything after it runs in the
+        dtype of `features`: the four weights, the forward sum, and (autograd of index_select) the index_add_ scatter
+        of the backward.  An invalid sample reads pixel 0 with four zero weights."""
+        B, C, H, W = features.shape
+        geo = roi_geometry_np(rois.detach().cpu().numpy(), H, W, aligned_height, aligned_width, spatial_scale)
+        n, S = geo["valid"].shape
+        dt = features.dtype
+        ok = torch.from_numpy(geo["valid"]).to(dt)
+        hr, wr = torch.from_numpy(geo["h_ratio"]).to(dt), torch.from_numpy(geo["w_ratio"]).to(dt)
+        base = torch.from_numpy(np.where(geo["valid"], geo["image"][:, None] * (H * W) + geo["off"], 0).astype(np.int64))
+        planes = features.permute(0, 2, 3, 1).reshape(B * H * W, C)
+        y = 0
+        for step, wt in ((0, (1 - hr) * (1 - wr)), (1, (1 - hr) * wr), (W, hr * (1 - wr)), (W + 1, hr * wr)):
+            y = y + (ok * wt).reshape(n * S, 1) * planes.index_select(0, (base + step).reshape(-1))
+        return y.reshape(n, aligned_height, aligned_width, C).permute(0, 3, 1, 2)
+
+    class _LiftTapsFn(object):
+        """ops._LiftTapsFn as the operator reads: z [N, 9 Mo, h, w], channel (dh * 3 + dw) * Mo + co = tap (dh, dw) of
+        output channel co; y = bias + sum over the taps of the (dh, dw) window of reflect_pad(lift(z_tap))."""
+
+        @staticmethod
+        def apply(z, bias, SH, SW):
+            Mo = z.shape[1] // 9
+            y = 0
+            for dh in range(3):
+                for dw in range(3):
+                    t = dh * 3 + dw
+                    up = F.interpolate(z[:, t * Mo:(t + 1) * Mo], size=(SH, SW), mode="bilinear", align_corners=True)
+                    y = y + F.pad(up, (1, 1, 1, 1), mode="reflect")[:, :, dh:dh + SH, dw:dw + SW]
+            return y if bias is None else y + bias.view(1, -1, 1, 1)
+
+    @staticmethod
+    def lift_stem_conv(seg, w, bias, size):
+        """the formula of tests/cpu_ops_shim.lift_stem_conv (reference model.py:1217-1226)"""
+        up = F.interpolate(seg, size=(size, size), mode="bilinear", align_corners=True)
+        return F.conv2d(F.pad(up, (1, 1, 1, 1), mode="reflect"), w, bias)
 
 
 REF = _Ref()
@@ -766,6 +859,233 @@ def run_lstm(ns, case, dtype, device):
 
 
 # =====================================================================================================================
+# ROIAlign: the ordered backward's per-image / per-slab decisions, and the scatter it falls back to
+# =====================================================================================================================
+# Boxes (`boxes`), in image coordinates (feature coordinates / scale), from the case's seeded generator:
+#   ("inside", n)    n boxes with every sample inside the map: x1, y1 >= 0 and x2 + 1, y2 + 1 <= W - 0.5, H - 0.5
+#   ("generic", n)   corners from -2 to 0.7 of the map, sizes up to 0.6 of it (as test_roi_align_bit_exact): partly outside
+#   ("tiny", n)      boxes of at most half a feature pixel, inside the map: their 36 samples share one to four anchors
+#   a list           explicit (x1, y1, x2, y2) rows
+# and their concatenation.  `imgs`: "sorted" (equal runs per image, as the existing tests), "random", or the explicit
+# list of image indices.  What the ordered backward decides for a case -- `table` (the workspace query is non-zero),
+# `staged` (per slab: "all", "none", or "last" = only the short last slab), `start_lds`, `taps` (the touched pixels have
+# at most ROI_SEQ taps: "seq", more: "many", or there are pixels of both regimes: "both") and `at_seq` (a pixel has
+# EXACTLY ROI_SEQ taps: the last one the one-lane loop takes) -- is stated here and proven from the geometry in
+# tests/test_kernel_edges_cpu.py.
+def _roi(cid, B, C, H, W, AH, AW, scale, boxes, imgs="sorted", table=True, staged="all", start_lds=True, taps="both",
+         at_seq=False, cols=5):
+    return dict(id=cid, B=B, C=C, H=H, W=W, AH=AH, AW=AW, scale=scale, boxes=boxes, imgs=imgs, table=table, staged=staged,
+                start_lds=start_lds, taps=taps, at_seq=at_seq, cols=cols)
+
+
+def _corner_box(H, W):
+    """samples at W - 3 .. W - 0.5 and H - 3 .. H - 0.5 (bin 0.5, exact in fp32): the last ones lie in the last row and
+    column, where hstart = H - 2 is the clamp and h_ratio = 1.5"""
+    return (W - 3.0, H - 3.0, W - 1.5, H - 1.5)
+
+
+ROI_CASES = [
+    _roi("unstaged-n_e-above-1024", 1, 2, 16, 16, 6, 6, 1.0, [("inside", 29)], staged="none", at_seq=True),
+    _roi("staged-n_e-exactly-1024", 1, 2, 16, 16, 4, 4, 1.0, [("inside", 64)]),
+    _roi("unstaged-n_e-1040", 1, 2, 16, 16, 4, 4, 1.0, [("inside", 65)], staged="none", at_seq=True),
+    # more than one image on the global-memory form of the tap: a roi's position in its image's list (g.x) is not its index
+    _roi("unstaged-rois-interleaved-1-0-1-0", 2, 2, 16, 16, 4, 4, 1.0, [("inside", 132)], imgs=[1, 0] * 66, staged="none",
+         at_seq=True),
+    _roi("unstaged-gradient-slab-C68-last-slab-nc4-staged", 1, 68, 8, 8, 6, 6, 1.0, [("generic", 15)], staged="last",
+         at_seq=True),
+    _roi("unstaged-many-taps", 1, 3, 16, 16, 6, 6, 1.0 / 16, [("tiny", 6), ("inside", 23)], staged="none", at_seq=True),
+    _roi("start-in-lds-at-limit-hw4607", 1, 2, 17, 271, 6, 6, 1.0, [("generic", 5), [_corner_box(17, 271)]], at_seq=True),
+    _roi("start-global-hw4608", 1, 2, 64, 72, 6, 6, 1.0, [("generic", 5), [_corner_box(64, 72)]], start_lds=False, at_seq=True),
+    _roi("C70-cpb8-last-slab-nc6", 2, 70, 8, 8, 6, 6, 0.5, [("generic", 6)], taps="seq"),
+    _roi("C63-cpb1", 2, 63, 8, 8, 6, 6, 0.5, [("generic", 6)], taps="seq"),
+    _roi("C64", 2, 64, 8, 8, 6, 6, 0.5, [("generic", 6)], at_seq=True),
+    _roi("images-0-and-1-own-no-roi", 3, 4, 8, 9, 6, 6, 1.0, [("generic", 5)], imgs=[2, 2, 2, 2, 2]),
+    _roi("rois-interleaved-2-0-1-2-0", 3, 4, 8, 9, 3, 3, 1.0, [("generic", 5)], imgs=[2, 0, 1, 2, 0], taps="seq"),
+    _roi("AH2xAW7", 2, 3, 12, 10, 2, 7, 1.0, [("generic", 4)], taps="seq"),
+    _roi("AH7xAW2", 2, 3, 12, 10, 7, 2, 1.0, [("generic", 4)], taps="seq"),
+    _roi("AH2xAW2", 2, 3, 12, 10, 2, 2, 1.0, [("generic", 4)], taps="seq"),
+    _roi("S256-16x16", 2, 3, 12, 10, 16, 16, 1.0, [("generic", 4)], at_seq=True),
+    # any valid sample has 0 <= h < 2: hstart = min(floor(h), 0) = 0, h_ratio up to 2
+    _roi("H2xW2-smallest-map", 2, 3, 2, 2, 6, 6, 1.0,
+         [[(0, 0, 0, 0), (0.2, 0.3, 0.5, 0.6), (-1, -1, 1.5, 1.5), (0.5, 0.5, 0.9, 0.8), (1, 1, 3, 3), (-3, 0, 0.5, 0.25)]],
+         taps="many"),
+    # integer boxes with bin 1: samples ON the pixels, from exactly 0 and up to exactly H - 1 = W - 1 = 7 (hstart = 6 by
+    # the clamp, h_ratio = 1); a box from -2 (its two leading rows and columns of samples are invalid); x2 < x1 - 1 (the
+    # width is clamped to 0: six samples per row on one column); the all-zero box slot (bin 0.2 from pixel 0)
+    _roi("last-row-and-column-exact", 1, 2, 8, 8, 6, 6, 1.0,
+         [[(2, 2, 6, 6), (0, 0, 4, 4), (0, 2, 4, 6), (-2, -2, 2, 2), (5, 1, 2, 5), (0, 0, 0, 0)]], at_seq=True),
+    _roi("every-sample-outside", 2, 2, 8, 8, 6, 6, 1.0,
+         [("generic", 2), [(9, 9, 12, 12), (-10, -10, -4, -4), (8, 2, 11, 5)]], imgs=[0, 0, 1, 1, 1], taps="seq"),
+    _roi("scatter-fallback-513-rois", 2, 2, 8, 8, 2, 2, 1.0, [("generic", 513)], imgs="random", table=False),
+    _roi("scatter-fallback-hw9216-lds", 1, 2, 96, 96, 6, 6, 1.0, [("generic", 4)], table=False),
+    _roi("table-path-320-rois-second-compaction-pass", 2, 2, 8, 8, 2, 2, 1.0, [("generic", 320)], imgs="random",
+         at_seq=True),
+]
+_ONE_BOX = [[(1, 1, 5, 5)]]
+ROI_REJECTED = [
+    _roi("17x16-S272-rejected", 1, 2, 8, 8, 17, 16, 1.0, _ONE_BOX),
+    _roi("AH1-rejected", 1, 2, 8, 8, 1, 6, 1.0, _ONE_BOX),
+    _roi("roi_cols4-rejected", 1, 2, 8, 8, 6, 6, 1.0, _ONE_BOX, cols=4),
+    _roi("map-1x8-rejected", 1, 2, 1, 8, 6, 6, 1.0, [[(1, 0, 5, 0)]]),
+    _roi("map-8x1-rejected", 1, 2, 8, 1, 6, 6, 1.0, [[(0, 1, 0, 5)]]),
+]
+
+
+def roi_inputs(case):
+    """(features [B, C, H, W], rois [n, cols], top gradient [n, C, AH, AW]) of a case, float32 on the CPU"""
+    g = _gen(case)
+    B, C, H, W, scale = case["B"], case["C"], case["H"], case["W"], case["scale"]
+    u = lambda n, lo, hi: lo + (hi - lo) * torch.rand(n, generator=g)
+    parts = []
+    for spec in case["boxes"]:
+        if isinstance(spec, list):
+            parts.append(torch.tensor(spec, dtype=torch.float32))
+            continue
+        kind, n = spec
+        if kind == "generic":
+            x1, y1 = u(n, -2.0, 0.7 * W), u(n, -2.0, 0.7 * H)
+            x2, y2 = x1 + u(n, 0.0, 0.6 * W), y1 + u(n, 0.0, 0.6 * H)
+        elif kind == "inside":
+            x1, y1 = u(n, 0.0, (W - 1.5) / 2), u(n, 0.0, (H - 1.5) / 2)
+            x2, y2 = x1 + u(n, 0.0, (W - 1.5) / 2), y1 + u(n, 0.0, (H - 1.5) / 2)
+        else:
+            x1, y1 = u(n, 1.0, W - 3.0), u(n, 1.0, H - 3.0)
+            x2, y2 = x1 + u(n, 0.0, 0.5), y1 + u(n, 0.0, 0.5)
+        parts.append(torch.stack([x1, y1, x2, y2], dim=1) / scale)
+    boxes = torch.cat(parts)
+    n = boxes.shape[0]
+    if case["imgs"] == "sorted":
+        img = torch.arange(n) * B // n
+    elif case["imgs"] == "random":
+        img = torch.randint(0, B, (n,), generator=g)
+    else:
+        img = torch.tensor(case["imgs"])
+    assert img.numel() == n and int(img.min()) >= 0 and int(img.max()) < B
+    rois = torch.cat([img.float().unsqueeze(1), boxes], dim=1)[:, :case["cols"]].contiguous()
+    feat = torch.randn(B, C, H, W, generator=g)
+    gtop = torch.randn(n, C, case["AH"], case["AW"], generator=g)
+    return feat, rois, gtop
+
+
+def run_roi(ns, case, dtype, device):
+    feat, rois, gtop = roi_inputs(case)
+    feat = _to(feat, dtype, device, True)
+    y = ns.roi_align(feat, rois.to(device), case["AH"], case["AW"], case["scale"])
+    y.backward(_to(gtop, dtype, device))
+    return {"y": y, "dfeat": feat.grad}
+
+
+def roi_facts(case):
+    """What roi_tap_table_kernel builds for every image of a case, from the geometry: nlist (its rois), n_e (their valid
+    samples), and of its touched pixels, by the length of their tap list (the four anchor ranges ranges() concatenates):
+    n_seq with at most ROI_SEQ taps, n_many with more, n_at_seq with exactly ROI_SEQ."""
+    _, rois, _ = roi_inputs(case)
+    H, W = case["H"], case["W"]
+    geo = roi_geometry_np(rois.numpy(), H, W, case["AH"], case["AW"], case["scale"])
+    out = []
+    for b in range(case["B"]):
+        mine = geo["image"] == b
+        ok = geo["valid"][mine]
+        cnt = np.bincount(geo["off"][mine][ok], minlength=H * W)
+        assert cnt.shape[0] == H * W
+        taps = cnt.copy()
+        for back in (1, W, W + 1):
+            taps[back:] += cnt[:H * W - back]
+        taps = taps[taps > 0]
+        out.append(dict(nlist=int(mine.sum()), n_e=int(ok.sum()), n_seq=int((taps <= ROI_SEQ).sum()),
+                        n_many=int((taps > ROI_SEQ).sum()), n_at_seq=int((taps == ROI_SEQ).sum())))
+    return out
+
+
+def roi_slabs(case):
+    """nc of every channel slab of roi_align_bwd_gather_kernel's grid"""
+    cpb = roi_cpb(case["C"])
+    return [min(cpb, case["C"] - c0) for c0 in range(0, case["C"], cpb)]
+
+
+def roi_slab_is_staged(case, facts, nc):
+    return facts["n_e"] <= ROI_LDS_SMP and facts["nlist"] * nc * case["AH"] * case["AW"] <= ROI_LDS_G
+
+
+def check_roi_backward_paths(ns, device, case, scatter, note=None):
+    """For a case of the table path: the ordered backward gives the same bits twice, and the atomic scatter
+    (`scatter(gtop, rois, case)` -> dfeat: objgan_roi_align_backward called directly on the same inputs) meets the fp64
+    reference under the bounds the ordered kernel meets -- so that neither path is only ever compared with the other."""
+    assert case["table"]
+    first = run_roi(ns, case, torch.float32, device)["dfeat"]
+    second = run_roi(ns, case, torch.float32, device)["dfeat"]
+    assert torch.equal(first, second), "roi:%s the ordered backward is not bit-reproducible" % case["id"]
+    _, rois, gtop = roi_inputs(case)
+    got = {"dfeat": scatter(gtop.to(device), rois.to(device), case)}
+    worst = compare("roi", case, got, note, only=("dfeat",), tag="scatter ")
+    exact_properties("roi", case, got)
+    return worst
+
+
+# =====================================================================================================================
+# layout-map stem: the four lift kernels alone (lift_taps), and behind the 1x1 convolution (lift_stem)
+# =====================================================================================================================
+# `longest`: the longest CSR row of ops._lift_axis_tables per axis (rows, columns) -- LIFT_MAXE entries are what an
+# adjoint thread keeps; tests/test_kernel_edges_cpu.py recomputes them.
+def _lift(cid, N, Mo, h, w, SH, SW, longest, bias=True):
+    return dict(id=cid, N=N, Mo=Mo, h=h, w=w, SH=SH, SW=SW, longest=longest, bias=bias)
+
+
+LIFT_TAPS_CASES = [
+    _lift("rows-3-to-8-longest-8", 2, 3, 3, 5, 8, 12, (8, 7)),
+    _lift("cols-4-to-11-longest-8", 1, 2, 6, 4, 13, 11, (6, 8)),
+    _lift("h1-rows-1-to-4-longest-8", 2, 2, 1, 3, 4, 4, (8, 4)),
+    _lift("identity-5-to-5", 2, 3, 5, 5, 5, 5, (4, 4)),
+    _lift("downscale-9x12-to-4x5", 2, 2, 9, 12, 4, 5, (2, 2)),
+    _lift("S2-smallest", 1, 1, 2, 2, 2, 2, (3, 3), bias=False),
+    _lift("second-grid-stride-trip", 4, 1, 363, 363, 726, 726, (6, 6)),
+]
+LIFT_TAPS_REJECTED = [
+    _lift("rows-3-to-9-longest-9-rejected", 1, 1, 3, 3, 9, 9, (9, 9)),
+    _lift("rows-1-to-5-longest-10-rejected", 1, 1, 1, 3, 5, 4, (10, 4)),
+    _lift("S1-rejected", 1, 1, 3, 3, 1, 1, (1, 1)),
+]
+
+
+def run_lift_taps(ns, case, dtype, device):
+    g = _gen(case)
+    N, Mo, h, w, SH, SW = (case[k] for k in ("N", "Mo", "h", "w", "SH", "SW"))
+    z = _to(torch.randn(N, 9 * Mo, h, w, generator=g), dtype, device, True)
+    bias = _to(torch.randn(Mo, generator=g), dtype, device, True) if case["bias"] else None
+    gy = _to(torch.randn(N, Mo, SH, SW, generator=g), dtype, device)
+    y = ns._LiftTapsFn.apply(z, bias, SH, SW)
+    y.backward(gy)
+    out = {"y": y, "dz": z.grad}
+    if bias is not None:
+        out["dbias"] = bias.grad
+    return out
+
+
+def _stem(cid, N, C, Mo, h, w, S, longest):
+    return dict(id=cid, N=N, C=C, Mo=Mo, h=h, w=w, SH=S, SW=S, longest=longest)
+
+
+LIFT_STEM_CASES = [
+    _stem("3x3-to-8-C7-Mo5-longest-8", 2, 7, 5, 3, 3, 8, (8, 8)),
+    _stem("5x9-to-12-C3-Mo2-rectangular-map", 2, 3, 2, 5, 9, 12, (7, 4)),
+    _stem("1x3-to-4-h1", 2, 4, 3, 1, 3, 4, (8, 4)),
+]
+
+
+def run_lift_stem(ns, case, dtype, device):
+    """data as test_lift_stem_conv_matches_the_reference_formulation: a layout map in [0, 1), a bank of unit response"""
+    g = _gen(case)
+    N, C, Mo, h, w, S = (case[k] for k in ("N", "C", "Mo", "h", "w", "SH"))
+    seg = _to(torch.rand(N, C, h, w, generator=g), dtype, device, True)
+    wt = _to(torch.randn(Mo, C, 3, 3, generator=g) / (C * 9) ** 0.5, dtype, device, True)
+    b = _to(torch.randn(Mo, generator=g), dtype, device, True)
+    gy = _to(torch.randn(N, Mo, S, S, generator=g), dtype, device)
+    y = ns.lift_stem_conv(seg, wt, b, S)
+    y.backward(gy)
+    return {"y": y, "dseg": seg.grad, "dw": wt.grad, "db": b.grad}
+
+
+# =====================================================================================================================
 # tables, references, the comparison
 # =====================================================================================================================
 FAMILIES = {
@@ -775,6 +1095,7 @@ FAMILIES = {
     "bmm": (BMM_CASES, run_bmm), "bce": (BCE_CASES, run_bce), "pool": (POOL_CASES, run_pool),
     "bilinear": (BILINEAR_CASES, run_bilinear), "fold": (FOLD_CASES, run_fold),
     "stream": (STREAM_CASES, run_stream), "lstm": (LSTM_CASES, run_lstm),
+    "roi": (ROI_CASES, run_roi), "lift_taps": (LIFT_TAPS_CASES, run_lift_taps), "lift_stem": (LIFT_STEM_CASES, run_lift_stem),
 }
 
 
@@ -789,10 +1110,24 @@ def case_ids(pairs):
 _CACHE = {}
 
 
+class _RoiOracle32(object):
+    """the fp32 oracle of ROIAlign stays the C restatement (oracle/roi_align_oracle.c), as the existing tests and
+    tests/cpu_ops_shim.roi_align use it: the forward is bit-equal to it"""
+
+    @staticmethod
+    def roi_align(*args):
+        import cpu_ops_shim
+        return cpu_ops_shim.roi_align(*args)
+
+
+ORACLE32 = {"roi": _RoiOracle32()}
+
+
 def _cached(kind, fam, case, dtype):
     key = (kind, fam, case["id"])
     if key not in _CACHE:
-        out = FAMILIES[fam][1](REF, case, dtype, torch.device("cpu"))
+        ns = ORACLE32.get(fam, REF) if kind == "oracle32" else REF
+        out = FAMILIES[fam][1](ns, case, dtype, torch.device("cpu"))
         _CACHE[key] = {k: v.detach().clone() for k, v in out.items()}
     return _CACHE[key]
 
@@ -806,26 +1141,28 @@ def oracle32(fam, case):
     return _cached("oracle32", fam, case, torch.float32)
 
 
-def compare(fam, case, got, note=None):
-    """e_k <= M * max(e_o, 2^-23) and the family's rel_l2 bound, for every tensor of the case.  Every figure is noted
-    before anything is asserted.  Returns the largest ratio e_k / max(e_o, 2^-23)."""
+def compare(fam, case, got, note=None, only=None, tag=""):
+    """e_k <= M * max(e_o, 2^-23) and the family's rel_l2 bound, for every tensor of the case (or those of `only`; `tag`
+    marks their lines in the log).  Every figure is noted before anything is asserted.  Returns the largest ratio
+    e_k / max(e_o, 2^-23)."""
     ref, o32 = reference(fam, case), oracle32(fam, case)
-    assert set(got) == set(ref), (sorted(got), sorted(ref))
+    names = sorted(ref) if only is None else sorted(only)
+    assert set(got) == set(names) <= set(ref), (sorted(got), sorted(ref))
     bad, worst = [], 0.0
-    for name in sorted(ref):
+    for name in names:
         e_k, e_o = max_err(got[name], ref[name]), max_err(o32[name], ref[name])
         ratio = e_k / max(e_o, EPS32)
         r2 = rel_l2(got[name], ref[name])
         worst = max(worst, ratio)
         if note is not None:
-            note("edge %s:%s %s" % (fam, case["id"], name), "e_k %.3g e_o %.3g ratio %.3g rel_l2 %.3g" % (e_k, e_o, ratio, r2))
+            note("edge %s%s:%s %s" % (tag, fam, case["id"], name), "e_k %.3g e_o %.3g ratio %.3g rel_l2 %.3g" % (e_k, e_o, ratio, r2))
         bound, mb = rl2_bound(fam, case, name), m_bound(fam, name)
         if not (e_k <= mb * max(e_o, EPS32)):
             bad.append("%s: e_k %.3g > %g * max(e_o %.3g, 2^-23)" % (name, e_k, mb, e_o))
         if not (r2 <= bound):
             bad.append("%s: rel_l2 %.3g > %g" % (name, r2, bound))
     if note is not None:
-        note("edge-max %s:%s" % (fam, case["id"]), "ratio %.3g" % worst)
+        note("edge-max %s%s:%s" % (tag, fam, case["id"]), "ratio %.3g" % worst)
     assert not bad, "%s:%s  %s" % (fam, case["id"], "; ".join(bad))
     return worst
 
@@ -860,6 +1197,13 @@ def exact_properties(fam, case, got):
         if case["tie"]:
             # slot 3's mask lives on the tied rectangle only, under slot 1's: the first maximum (slot 1) takes it all
             assert float(got["df"].detach().cpu()[:, :, 3].abs().sum()) == 0.0, "the second of two tied slots received gradient"
+    elif fam == "roi":
+        if "y" in got:
+            assert torch.equal(got["y"].detach().cpu(), o32["y"]), "roi_align forward is not bit-equal to the C oracle"
+        # a pixel no valid sample touches (a whole image without rois or with every sample outside; a tap whose weight
+        # is exactly 0) receives exactly nothing
+        untouched = reference(fam, case)["dfeat"] == 0
+        assert float(got["dfeat"].detach().cpu()[untouched].abs().sum()) == 0.0, "gradient where the reference has exactly 0"
 
 
 def work_items(fam, case):
@@ -874,7 +1218,15 @@ def work_items(fam, case):
         return N * C * ((H - case["k"]) // case["s"] + 1) * ((W - case["k"]) // case["s"] + 1)
     if fam == "bilinear":
         return case["shape"][0] * case["shape"][1] * case["out"][0] * case["out"][1]
+    if fam == "lift_taps":
+        return min(lift_launch_items(case))
     return case["n"]
+
+
+def lift_launch_items(case):
+    """work items of the four launches of the lift kernels: columns forward / rows backward, rows forward, columns backward"""
+    N, h, w, SH, SW = (case[k] for k in ("N", "h", "w", "SH", "SW"))
+    return (N * h * SW, N * SH * SW, N * h * SW, N * h * w)
 
 
 def check_case(ns, device, fam, case, note=None):
