@@ -68,36 +68,38 @@ def _mixture(raw, K):
     return torch.softmax(pi, dim=1), ua, ub, torch.exp(sa), torch.exp(sb), torch.tanh(rho)
 
 
-def _draw(params, u, z1, z2):
+def _draw(params, u, z1, z2, ft=np.float32):
     pi, ua, ub, sa, sb, rho = (p[0].numpy() for p in params)
-    p = np.log(pi) / np.float32(0.4)
+    p = np.log(pi) / ft(0.4)
     p = np.exp(p - p.max())
     p = p / p.sum()
     k, edge = choose_component(p, u)
-    t = np.float32(np.sqrt(0.4))
-    s1, s2 = np.float32(sa[k] * t), np.float32(sb[k] * t)
+    t = ft(np.sqrt(0.4))
+    s1, s2 = ft(sa[k] * t), ft(sb[k] * t)
     cov = [[s1 * s1, (rho[k] * s1) * s2], [(rho[k] * s1) * s2, s2 * s2]]
     a, b = cholesky_point([ua[k], ub[k]], cov, z1, z2)
     return a, b, edge
 
 
-def decode_ref(sd, h0, c0, noise, first_input, sos, eos, K):
+def decode_ref(sd, h0, c0, noise, first_input, sos, eos, K, dtype=torch.float32):
     """sd: decoder state dict (fp32, CPU); h0, c0 [B, H]; noise [B, T, 6] float64.
     -> labels [B, T] int32, lengths [B] int32, samples [B, T, 4] float64, trace [B, T, L + 12K] float32 (zero past
-    each length), label margins [B] and edge margins [B] (the smallest over the caption's steps)."""
-    sd = {k: v.detach().float().cpu() for k, v in sd.items()}
+    each length), label margins [B] and edge margins [B] (the smallest over the caption's steps).
+    dtype=torch.float64: the same formulas with no fp32 rounding anywhere (the trace is float64 then)."""
+    ft = np.float32 if dtype == torch.float32 else np.float64
+    sd = {k: v.detach().to(dtype).cpu() for k, v in sd.items()}
     noise = np.asarray(noise, dtype=np.float64)
     B, T = noise.shape[0], noise.shape[1]
     L = sd["l_out.weight"].shape[0]
     labels = np.zeros((B, T), dtype=np.int32)
     lengths = np.zeros((B,), dtype=np.int32)
     samples = np.zeros((B, T, 4), dtype=np.float64)
-    trace = np.zeros((B, T, L + 12 * K), dtype=np.float32)
+    trace = np.zeros((B, T, L + 12 * K), dtype=ft)
     lmargin = np.full((B,), np.inf)
     emargin = np.full((B,), np.inf)
-    f32 = lambda *v: torch.tensor([list(v)], dtype=torch.float32)
+    f32 = lambda *v: torch.tensor([[float(e) for e in v]], dtype=dtype)
     for b in range(B):
-        h, c = h0[b:b + 1].float().cpu(), c0[b:b + 1].float().cpu()
+        h, c = h0[b:b + 1].to(dtype).cpu(), c0[b:b + 1].to(dtype).cpu()
         x, y, w, r = (np.float32(v) for v in first_input)
         label = sos
         for t in range(T):
@@ -115,16 +117,16 @@ def decode_ref(sd, h0, c0, noise, first_input, sos, eos, K):
             lmargin[b] = min(lmargin[b], float(torch.log(top.values[0].double()) - torch.log(top.values[1].double())))
             xy_hidden = torch.cat((h, ps), dim=1)
             xy_par = _mixture(F.linear(xy_hidden, sd["xy_out.weight"], sd["xy_out.bias"]), K)
-            xs, ys, e1 = _draw(xy_par, *noise[b, t, 0:3])
-            nxy = F.linear(f32(np.float32(xs), y), sd["next_xy_embedding.weight"], sd["next_xy_embedding.bias"])
+            xs, ys, e1 = _draw(xy_par, *noise[b, t, 0:3], ft=ft)
+            nxy = F.linear(f32(ft(xs), y), sd["next_xy_embedding.weight"], sd["next_xy_embedding.bias"])
             wh_par = _mixture(F.linear(torch.cat((xy_hidden, nxy), dim=1), sd["wh_out.weight"], sd["wh_out.bias"]), K)
-            ws, hs, e2 = _draw(wh_par, *noise[b, t, 3:6])
+            ws, hs, e2 = _draw(wh_par, *noise[b, t, 3:6], ft=ft)
             emargin[b] = min(emargin[b], e1, e2)
             labels[b, t] = label
             samples[b, t] = (xs, ys, ws, hs)
             trace[b, t] = torch.cat((ps,) + xy_par + wh_par, dim=1)[0].numpy()
             lengths[b] = t + 1
-            x, y, w, r = np.float32(xs), np.float32(ys), np.float32(ws), np.float32(hs)
+            x, y, w, r = ft(xs), ft(ys), ft(ws), ft(hs)
             if label == eos:
                 break
     return labels, lengths, samples, trace, lmargin, emargin

@@ -47,18 +47,22 @@ def pdf(par, x, y):
     return torch.log((pi * torch.exp(a - a_max) / norm).sum() + 1e-5) + a_max
 
 
-def step_ref(sd, h0, c0, labels, boxes, lens, first_input, weight, lamda1, lamda2, K, dtype=torch.float64, grad=True):
+def step_ref(sd, h0, c0, labels, boxes, lens, first_input, weight, lamda1, lamda2, K, dtype=torch.float64, grad=True,
+             dtrace=False, pad=0):
     """sd: decoder state dict; h0, c0 [B, H]; labels [B, T + 1] ints; boxes [B, T + 1, 4]; lens [B]; weight [L].
     -> dict: trace [B, T, L + 12K] (zero past each length), sums [B, 3] (label term, box term, n), loss, matches [B],
-    grads {key: tensor} of the batch loss, margins (the smallest distance factors from the two clamps)."""
+    grads {key: tensor} of the batch loss, margins (the smallest distance factors from the two clamps).
+    pad: the label whose weight is zero and that n and matches leave out (the box mask stays label != 0).
+    dtrace=True (with grad) adds "dtrace" [B, T, L + 12K]: per (b, t) the gradient of the batch loss with respect to the
+    UNCLAMPED softmax (zero where the clamp is active) and to the activated mixture parameters; zero past a length."""
     p = {k: v.detach().to(dtype).clone().requires_grad_(grad) for k, v in sd.items()}
     labels = torch.as_tensor(labels).long()
     boxes = torch.as_tensor(boxes).to(dtype)
     weight = torch.as_tensor(weight).to(dtype).clone()
-    weight[0] = 0
+    weight[pad] = 0
     B, T = labels.shape[0], labels.shape[1] - 1
     L = p["l_out.weight"].shape[0]
-    rows, lsum, bsum, ns, matches = [], [], [], [], []
+    rows, lsum, bsum, ns, matches, nodes = [], [], [], [], [], []
     label_margin, norm_margin = math.inf, math.inf
     for b in range(B):
         h, c = h0[b].to(dtype), c0[b].to(dtype)
@@ -86,9 +90,11 @@ def step_ref(sd, h0, c0, labels, boxes, lens, first_input, weight, lamda1, lamda
                            p["next_xy_embedding.bias"])
             wh = mixture(F.linear(torch.cat((xy_hidden, nxy)), p["wh_out.weight"], p["wh_out.bias"]), K)
             caption.append(torch.cat((ps,) + xy + wh))
+            nodes.append((b, t, (soft,) + xy + wh))
             lt = lt - weight[nl] * ps[nl]
             if nl != 0:
                 bt = bt - pdf(xy, boxes[b, t + 1, 0], boxes[b, t + 1, 1]) - pdf(wh, boxes[b, t + 1, 2], boxes[b, t + 1, 3])
+            if nl != pad:
                 n += 1
                 m += int(int(torch.argmax(ps)) == nl)
             with torch.no_grad():
@@ -105,18 +111,28 @@ def step_ref(sd, h0, c0, labels, boxes, lens, first_input, weight, lamda1, lamda
     N = sum(ns)
     loss = (lamda1 * sum(lsum) + lamda2 * sum(bsum)) / N
     grads = None
-    if grad:
-        got = torch.autograd.grad(loss, list(p.values()), allow_unused=True)
-        grads = {k: (torch.zeros_like(v) if g is None else g) for (k, v), g in zip(p.items(), got)}
     TR = L + 12 * K
+    dtr = None
+    if grad:
+        flat = [v for _, _, row in nodes for v in row] if dtrace else []
+        got = torch.autograd.grad(loss, list(p.values()) + flat, allow_unused=True)
+        grads = {k: (torch.zeros_like(v) if g is None else g) for (k, v), g in zip(p.items(), got)}
+        if dtrace:
+            dtr = torch.zeros((B, T, TR), dtype=dtype)
+            got = iter(got[len(p):])
+            for b, t, row in nodes:
+                dtr[b, t] = torch.cat([torch.zeros_like(v) if g is None else g for v, g in zip(row, got)])
     trace = torch.zeros((B, T, TR), dtype=dtype)
     for b, caption in enumerate(rows):
         for t, row in enumerate(caption):
             trace[b, t] = row.detach()
     val = lambda v: float(v.detach()) if torch.is_tensor(v) else float(v)
     sums = torch.tensor([[val(l), val(x), n] for l, x, n in zip(lsum, bsum, ns)], dtype=torch.float64)
-    return {"trace": trace, "sums": sums, "loss": val(loss), "matches": matches, "grads": grads,
-            "label_margin": label_margin, "norm_margin": norm_margin}
+    out = {"trace": trace, "sums": sums, "loss": val(loss), "matches": matches, "grads": grads,
+           "label_margin": label_margin, "norm_margin": norm_margin}
+    if dtr is not None:
+        out["dtrace"] = dtr
+    return out
 
 
 # kernel layout <-> state dict: the order of the 17 tensors of objgan_box_decode and which of them are transposed
