@@ -490,6 +490,35 @@ int objgan_snapshot_grid(const float* imgs, const float* lr_imgs, const float* a
                          int nvis, int T, int a, int vis, int H, int W, int LH, int LW,
                          int max_word_num, int font_max, int per_panel_norm, void* stream);
 
+/* ---- shape generator training (csrc/convlstm.hip; reference shape_generation/model.py:81-128, miscc/losses.py,
+ * datasets.py:99-111).  The ConvLSTM recurrence is split: the input part of the gate convolution runs once over all
+ * B R maps of a direction, only the hidden part stays in the loop; these entries are the point-wise rest of a step.
+ * Ch hidden channels, HW pixels per map; gate order in, remember, out, cell.  16-byte accesses when HW and the strides
+ * are multiples of four floats and the pointers are 16-byte aligned, scalar accesses otherwise; no float atomics.
+ * cell_forward: gx = the input-part gates of this step, image b at gx + b gx_bstride ([4 Ch][HW]); gh [B][4 Ch][HW] the
+ *     hidden-part convolution (NULL at t = 0); c_prev [B][Ch][HW] (NULL: zero).  Writes h twice -- h_out [B][Ch][HW]
+ *     (the next step's convolution input) and image b's slot of the state slab at h_slab + b slab_bstride --, c_out
+ *     [B][Ch][HW] and acts [B][5 Ch][HW]: the four activated gates, then tanh(c).
+ * cell_backward: dh = dh_slab[b dh_bstride] (+ dh_rec [B][Ch][HW], NULL at the last step); dc_in (NULL: zero); writes
+ *     the pre-activation gate gradients to dg_slab + b dg_bstride ([4 Ch][HW], the slot of the batch-major slab the
+ *     input-part gradients are taken from in one launch) and to dg_out [B][4 Ch][HW], and dc_out = dc f.
+ *     c_prev NULL (t = 0): the remember gate's gradient is zero.
+ * box_max: y[b][i] = max over r of x[b][r][i], i < CSS; arg (uint8, may be NULL in the forward) the FIRST maximal r,
+ *     which is where the backward puts dy; every element of dx is written.  R <= 255.
+ * boxmaps_onehot: raw [B][NB][SS] per-box maps, cat [B][NB] category of each slot, num [B] boxes per image ->
+ *     fwd, bwd [B][R][C][SS]: fwd[b][r][cat[b][r]] = raw[b][r] for r < num[b]; bwd[b][r] = fwd's slot NB - 1 - r (the
+ *     sequence reversed over all NB slots, then cut to R <= NB). */
+int objgan_convlstm_cell_forward(const float* gx, const float* gh, const float* c_prev, float* h_out, float* h_slab,
+                                 float* c_out, float* acts, int B, int Ch, int HW, long gx_bstride, long slab_bstride,
+                                 void* stream);
+int objgan_convlstm_cell_backward(const float* dh_slab, const float* dh_rec, const float* dc_in, const float* acts,
+                                  const float* c_prev, float* dg_slab, float* dg_out, float* dc_out, int B, int Ch, int HW,
+                                  long dh_bstride, long dg_bstride, void* stream);
+int objgan_box_max_forward(const float* x, float* y, unsigned char* arg, int B, int R, long CSS, void* stream);
+int objgan_box_max_backward(const float* dy, const unsigned char* arg, float* dx, int B, int R, long CSS, void* stream);
+int objgan_boxmaps_onehot(const float* raw, const int* cat, const int* num, float* fwd, float* bwd, int B, int NB, int R,
+                          int C, int SS, void* stream);
+
 /* ---- measurement aid (bench.py roofline leg): hipEvent-bracketed conv launches ------------------ */
 int objgan_prof_enable(int on);
 int objgan_prof_collect(double* ms, double* flops, long* count);   /* arrays of 192 categories (48..95: fp16x2 instances; 96..191: fp16x2 on records, one / two pixel groups) */

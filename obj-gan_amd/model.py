@@ -597,6 +597,8 @@ class SHP_G_NET(nn.Module):
     """Box layouts -> per-box instance masks: bidirectional ConvLSTM over the box sequence at
     16x16, residual blocks, two upBlocks back to 64x64 (reference model.py:898-985)."""
 
+    split_recurrence = True     # training path; False: the per-step cat + conv cell loop under autograd (tools/shapegen_time.py)
+
     def __init__(self, num_classes):
         super(SHP_G_NET, self).__init__()
         self.nbf = num_classes
@@ -626,6 +628,12 @@ class SHP_G_NET(nn.Module):
             h = self.downsample2(self.downsample1(maps.reshape(-1, self.nbf, S, S)))
             return h.view(B, R, -1, fm, fm)
         h_fwd, h_bwd = down(bbox_maps_fwd), down(bbox_maps_bwd)
+        if torch.is_grad_enabled() and self.split_recurrence:
+            # training: the recurrence split into one input-part launch per direction and a hidden-part conv per step;
+            # the states land in their slots of the [B, R, 2 nbf, fm, fm] slabs jointConv's input is assembled from
+            fwd = ops.convlstm_sequence(h_fwd, self.fwd_convlstm.Gates.weight, self.fwd_convlstm.Gates.bias)
+            bwd = ops.convlstm_sequence(h_bwd, self.bwd_convlstm.Gates.weight, self.bwd_convlstm.Gates.bias, reverse=True)
+            return self._tail(torch.cat((fwd, bwd, z), 2), bbox_fmaps, B, R, fm, S)
         state_fwd, state_bwd, fwd_lst, bwd_lst = None, None, [], []
         for t in range(R):
             state_fwd = self.fwd_convlstm(h_fwd[:, t], state_fwd)
@@ -633,11 +641,72 @@ class SHP_G_NET(nn.Module):
             state_bwd = self.bwd_convlstm(h_bwd[:, t], state_bwd)
             bwd_lst.append(state_bwd[0].unsqueeze(1))
         h_code = torch.cat([torch.cat((fwd_lst[t], bwd_lst[R - t - 1], z[:, t:t + 1]), 2) for t in range(R)], 1)
+        return self._tail(h_code, bbox_fmaps, B, R, fm, S)
+
+    def _tail(self, h_code, bbox_fmaps, B, R, fm, S):
         h_code = self.jointConv(h_code.view(B * R, -1, fm, fm))
         h_code = h_code * bbox_fmaps.reshape(B * R, 1, fm, fm)            # crop to the box
         h_code = self.residual(h_code)
         h_code = self.upsample2(self.upsample1(h_code))
         return self.img_net(h_code).view(B, R, -1, S, S)
+
+
+# ---------------------------------------------------------------------------------------------
+# discriminators of the shape generator's training (reference shape_generation/model.py:233-276): same state-dict keys
+# (`downsample1.0.weight`, `get_logits.outlogits.0.bias`), so the reference's netINSD.pth / netGLBD.pth load.
+# ---------------------------------------------------------------------------------------------
+def downBlock_4x4(in_planes, out_planes):
+    return _ActSeq(nn.Conv2d(in_planes, out_planes, kernel_size=4, stride=2, padding=1, bias=False),
+                   nn.InstanceNorm2d(out_planes),
+                   nn.LeakyReLU(0.2, inplace=True))
+
+
+class SHP_GET_LOGITS(nn.Module):
+    """[Conv2d(nbf / 16, 1, k4, s4, bias), Sigmoid] on the 4x4 code: a dot product with the flattened map."""
+
+    def __init__(self, nbf):
+        super(SHP_GET_LOGITS, self).__init__()
+        self.outlogits = nn.Sequential(nn.Conv2d(nbf // 16, 1, kernel_size=4, stride=4), nn.Sigmoid())
+
+    def forward(self, h_code):
+        conv = self.outlogits[0]
+        if h_code.shape[2] != 4 or h_code.shape[3] != 4:
+            raise ValueError("SHP_GET_LOGITS: the code is a 4x4 map (got %s)" % (tuple(h_code.shape),))
+        w = conv.weight.view(1, -1)
+        cell = getattr(conv.weight, "_og_epoch", None)
+        if cell is not None:
+            w._og_epoch = cell
+        return ops.linear(h_code.reshape(h_code.shape[0], -1), w, conv.bias, act="sigmoid").view(-1, 1, 1, 1)
+
+
+class _ShapeGenD(nn.Module):
+    def __init__(self, num_classes):
+        super(_ShapeGenD, self).__init__()
+        self.nbf = num_classes
+        self.downsample1 = downBlock_4x4(self.nbf + 1, self.nbf // 2)
+        self.downsample2 = downBlock_4x4(self.nbf // 2, self.nbf // 4)
+        self.downsample3 = downBlock_4x4(self.nbf // 4, self.nbf // 8)
+        self.downsample4 = downBlock_4x4(self.nbf // 8, self.nbf // 16)
+        self.get_logits = SHP_GET_LOGITS(self.nbf)
+
+    def forward(self, x_var, maps=None):
+        """x_var [N, nbf + 1, S, S], or the mask [N, 1, S, S] with the box maps [N, nbf, S, S] as the second part of the
+        first convolution's input: no concatenated tensor, and no gradient to the maps"""
+        conv = self.downsample1[0]
+        if maps is None:
+            y = ops.conv2d(x_var, conv.weight, None, 2, 1, "zeros")
+        else:
+            y = ops.conv2d_cat(x_var, maps, conv.weight, 2, 1)
+        x = _in_act(y, self.downsample1[1], "lrelu")
+        return self.downsample4(self.downsample3(self.downsample2(x)))
+
+
+class INS_D_NET(_ShapeGenD):
+    pass
+
+
+class GLB_D_NET(_ShapeGenD):
+    pass
 
 
 def Block3x3_leakRelu(in_planes, out_planes):

@@ -97,6 +97,11 @@ SIGNATURES = {
     "objgan_jpeg_decode": [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_long, _ptr, _ptr, _ptr],
     "objgan_snapshot_blend_table": [_ptr],
     "objgan_snapshot_grid": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_long] + [_c_int] * 11 + [_ptr],
+    "objgan_convlstm_cell_forward": [_ptr] * 7 + [_c_int] * 3 + [_c_long] * 2 + [_ptr],
+    "objgan_convlstm_cell_backward": [_ptr] * 8 + [_c_int] * 3 + [_c_long] * 2 + [_ptr],
+    "objgan_box_max_forward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
+    "objgan_box_max_backward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
+    "objgan_boxmaps_onehot": [_ptr] * 5 + [_c_int] * 5 + [_ptr],
     "objgan_prof_enable": [_c_int],
     "objgan_conv_bank_layout": [_c_int] * 10,
     "objgan_conv_wgrad_rec_ok": [_c_int] * 8,

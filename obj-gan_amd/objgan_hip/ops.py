@@ -2393,3 +2393,163 @@ def adam_step_gated_(p, g, m, v, lr, beta1, beta2, eps, state, flag, coef, grad_
 def ema_update_(avg, p, decay):
     _chk(avg, p)
     _lib.call("objgan_ema_update", _p(avg), _p(p), p.numel(), float(decay), float(1.0 - decay), _stream())
+
+
+# ----------------------------------------------------------------------------------------------
+# shape generator training: split ConvLSTM recurrence, box-axis max, one-hot box maps (csrc/convlstm.hip)
+# ----------------------------------------------------------------------------------------------
+def _off(t, floats):
+    return ctypes.c_void_p(t.data_ptr() + 4 * int(floats))
+
+
+def _gate_slices(w, Cin):
+    """(input part, hidden part) of a ConvLSTM gate bank [4 Ch, Cin + Ch, k, k] and whether their packed banks may be kept"""
+    wx, okx = _w_slice(w, 0, Cin)
+    wh, okh = _w_slice(w, Cin, w.shape[1])
+    for s, ok in ((wx, okx), (wh, okh)):
+        if not ok:
+            s._og_nocache = True
+    return wx, okx, wh, okh
+
+
+def convlstm_cell_forward_(gx, gx_bstride, gh, c_prev, h_out, h_slab, slab_bstride, c_out, acts, B, Ch, HW):
+    """raw objgan_convlstm_cell_forward: gx / h_slab are ctypes addresses (a step's slot of a larger tensor)"""
+    _chk(gh, c_prev, h_out, c_out, acts)
+    _lib.call("objgan_convlstm_cell_forward", gx, _p(gh), _p(c_prev), _p(h_out), h_slab, _p(c_out), _p(acts),
+              int(B), int(Ch), int(HW), int(gx_bstride), int(slab_bstride), _stream())
+
+
+def convlstm_cell_backward_(dh_slab, dh_bstride, dh_rec, dc_in, acts, c_prev, dg_slab, dg_bstride, dg_out, dc_out, B, Ch, HW):
+    """raw objgan_convlstm_cell_backward: dh_slab / dg_slab are ctypes addresses"""
+    _chk(dh_rec, dc_in, acts, c_prev, dg_out, dc_out)
+    _lib.call("objgan_convlstm_cell_backward", dh_slab, _p(dh_rec), _p(dc_in), _p(acts), _p(c_prev), dg_slab, _p(dg_out),
+              _p(dc_out), int(B), int(Ch), int(HW), int(dh_bstride), int(dg_bstride), _stream())
+
+
+class _ConvLstmSeqFn(torch.autograd.Function):
+    """ConvLSTM over a box sequence (reference shape_generation/model.py:81-128, 194-202) with the recurrence split:
+    gates_t = conv3x3(x_t, W[:, :Cin]) + b + conv3x3(h_{t-1}, W[:, Cin:]).  The input part runs ONCE over all B R maps,
+    the hidden part per step (none at t = 0: h_{-1} = 0), the rest of a step is one point-wise launch.  Backward: per
+    step the point-wise launch and the hidden-part data gradient; the input-part data / weight / bias gradients and the
+    hidden-part weight gradient are one launch each over the whole sequence."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, reverse):
+        _chk(x, w, bias)
+        x = _c(x)
+        B, R, Cin, H, W = x.shape
+        Ch = w.shape[0] // 4
+        k = w.shape[2]
+        if w.shape[0] != 4 * Ch or w.shape[1] != Cin + Ch or k != w.shape[3] or k % 2 != 1 or R > 255:
+            raise _lib.ObjganHipError("convlstm_sequence: bad gate bank %s for input %s" % (tuple(w.shape), tuple(x.shape)))
+        pad = k // 2
+        HW = H * W
+        wx, okx, wh, okh = _gate_slices(w, Cin)
+        dev = x.device
+        x2 = x.view(B * R, Cin, H, W)
+        gx = _conv_fwd(x2, wx, bias, 1, pad, 0, False, None)                 # [B R, 4 Ch, H, W], image-major
+        hs = torch.empty((R, B, Ch, H, W), dtype=_F32, device=dev)           # step-major: h_{t-1} is a contiguous conv input
+        cs = torch.empty((R, B, Ch, H, W), dtype=_F32, device=dev)
+        acts = torch.empty((R, B, 5 * Ch, H, W), dtype=_F32, device=dev)
+        slab = torch.empty((B, R, Ch, H, W), dtype=_F32, device=dev)
+        for t in range(R):
+            gh = _conv_fwd(hs[t - 1], wh, None, 1, pad, 0, False, None) if t else None
+            slot = R - 1 - t if reverse else t
+            convlstm_cell_forward_(_off(gx, t * 4 * Ch * HW), R * 4 * Ch * HW, gh, cs[t - 1] if t else None, hs[t],
+                                   _off(slab, slot * Ch * HW), R * Ch * HW, cs[t], acts[t], B, Ch, HW)
+        ctx.cfg = (bool(reverse), pad, k, okx, okh)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x2, w, hs, cs, acts)
+        return slab
+
+    @staticmethod
+    def backward(ctx, dslab):
+        x2, w, hs, cs, acts = ctx.saved_tensors
+        reverse, pad, k, _, _ = ctx.cfg
+        R, B, Ch, H, W = hs.shape
+        Cin = x2.shape[1]
+        HW = H * W
+        dslab = _c(dslab)
+        _chk(dslab)
+        dev = dslab.device
+        wx, okx, wh, okh = _gate_slices(w, Cin)
+        dgs = torch.empty((B, R, 4 * Ch, H, W), dtype=_F32, device=dev)      # image-major: the input part's gradients, one launch
+        dgt = torch.empty((R, B, 4 * Ch, H, W), dtype=_F32, device=dev)      # step-major: the hidden part's
+        dh_rec = dc = None
+        for t in range(R - 1, -1, -1):
+            slot = R - 1 - t if reverse else t
+            dc_new = torch.empty((B, Ch, H, W), dtype=_F32, device=dev)
+            convlstm_cell_backward_(_off(dslab, slot * Ch * HW), R * Ch * HW, dh_rec, dc, acts[t], cs[t - 1] if t else None,
+                                    _off(dgs, t * 4 * Ch * HW), R * 4 * Ch * HW, dgt[t], dc_new, B, Ch, HW)
+            dc = dc_new
+            if t:
+                dh_rec = _conv_dgrad(dgt[t], wh, B, Ch, H, W, 1, pad, 0, False, cacheable=okh)
+        dg2 = dgs.view(B * R, 4 * Ch, H, W)
+        dx = dw_ = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _conv_dgrad(dg2, wx, B * R, Cin, H, W, 1, pad, 0, False, cacheable=okx).view(B, R, Cin, H, W)
+        if ctx.needs_input_grad[1]:
+            dwx = _conv_wgrad(x2, dg2, 4 * Ch, k, 1, pad, 0, False)
+            if R > 1:
+                dwh = _conv_wgrad(hs[:R - 1].view((R - 1) * B, Ch, H, W), dgt[1:].view((R - 1) * B, 4 * Ch, H, W),
+                                  4 * Ch, k, 1, pad, 0, False)
+            else:
+                dwh = torch.zeros((4 * Ch, Ch, k, k), dtype=_F32, device=dev)
+            dw_ = torch.cat([dwx, dwh], dim=1)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = torch.empty(4 * Ch, dtype=_F32, device=dev)
+            _channel_sum(dg2, db, B * R, 4 * Ch, HW)
+        return dx, dw_, db, None
+
+
+def convlstm_sequence(x, w, bias=None, reverse=False):
+    """x [B, R, Cin, H, W], gate bank w [4 Ch, Cin + Ch, k, k] (gate order in, remember, out, cell) -> the hidden states
+    [B, R, Ch, H, W]; step t's state sits in slot t, or in slot R - 1 - t when `reverse`."""
+    return _ConvLstmSeqFn.apply(x, w, bias, bool(reverse))
+
+
+class _BoxMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _chk(x)
+        x = _c(x)
+        B, R = x.shape[0], x.shape[1]
+        css = x[0, 0].numel()
+        y = torch.empty((B,) + tuple(x.shape[2:]), dtype=_F32, device=x.device)
+        arg = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+        _lib.call("objgan_box_max_forward", _p(x), _p(y), _p(arg), B, R, css, _stream())
+        ctx.save_for_backward(arg)
+        ctx.R = R
+        ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    def backward(ctx, dy, _darg):
+        (arg,) = ctx.saved_tensors
+        dy = _c(dy)
+        _chk(dy)
+        B, R = dy.shape[0], ctx.R
+        dx = torch.empty((B, R) + tuple(dy.shape[1:]), dtype=_F32, device=dy.device)
+        _lib.call("objgan_box_max_backward", _p(dy), _p(arg), _p(dx), B, R, dy[0].numel(), _stream())
+        return dx
+
+
+def box_max(x, return_arg=False):
+    """torch.max(x, 1)[0] over the box axis of [B, R, ...]; the gradient goes to the FIRST maximal box"""
+    y, arg = _BoxMaxFn.apply(x)
+    return (y, arg) if return_arg else y
+
+
+def boxmaps_onehot(raw, cats, num_rois, R, C):
+    """raw [B, NB, S, S] per-box maps, cats [B, NB] int32, num_rois [B] int32 -> (bbox_maps_fwd, bbox_maps_bwd)
+    [B, R, C, S, S]; the backward sequence is the forward one reversed over all NB slots, then cut to R"""
+    _chk(raw)
+    raw = _c(raw)
+    if cats.dtype != torch.int32 or num_rois.dtype != torch.int32 or not cats.is_cuda or not num_rois.is_cuda:
+        raise _lib.ObjganHipError("boxmaps_onehot: cats and num_rois are int32 tensors on the GPU")
+    B, NB, S1, S2 = raw.shape
+    fwd = torch.empty((B, int(R), int(C), S1, S2), dtype=_F32, device=raw.device)
+    bwd = torch.empty_like(fwd)
+    _lib.call("objgan_boxmaps_onehot", _p(raw), _p(_c(cats)), _p(_c(num_rois)), _p(fwd), _p(bwd), B, NB, int(R), int(C),
+              S1 * S2, _stream())
+    return fwd, bwd

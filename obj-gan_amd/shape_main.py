@@ -1,0 +1,97 @@
+"""Command line of the shape generator's training: the reference's `shape_generation/main.py --FLAG` (main.py:24-111).
+
+    python shape_main.py --FLAG --PCP_LAMBDA 0 --data_dir ../data/coco --output_dir ..
+
+Same arguments.  Refused, loudly: a non-zero --PCP_LAMBDA (the perceptual VGG-19 term is not built yet; the reference's
+default of 10 therefore has to be overridden with `--PCP_LAMBDA 0`) and a run without --FLAG (the reference's
+single-PNG inspection dump is not built).  The run happens on the GPU: `--gpu` names the device (default 0; the
+reference's `-1` CPU mode does not exist here).
+"""
+import argparse
+import datetime
+import os
+import pprint
+import random
+import sys
+import time
+
+import numpy as np
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description='Train a shape generation network')
+    parser.add_argument('--gpu', dest='gpu_ids', type=str, default='0')
+    parser.add_argument('--data_dir', dest='data_dir', type=str, default='../data/coco')
+    parser.add_argument('--manualSeed', type=int, help='manual seed')
+    parser.add_argument('--output_dir', type=str, default='..')
+    parser.add_argument('--MAX_EPOCH', type=int, default=60)
+    parser.add_argument('--WORKERS', type=int, default=0)
+    parser.add_argument('--NET_G', type=str, default='')
+    parser.add_argument('--DISCRIMINATOR_LR', type=float, default=0.0002)
+    parser.add_argument('--GENERATOR_LR', type=float, default=0.0002)
+    parser.add_argument('--INS_LAMBDA', type=float, default=1.0)
+    parser.add_argument('--GLB_LAMBDA', type=float, default=1.0)
+    parser.add_argument('--PCP_LAMBDA', type=float, default=10.0)
+    parser.add_argument('--R_NUM', type=int, default=1)
+    parser.add_argument('--BATCH_SIZE', type=int, default=40)
+    parser.add_argument('--FLAG', dest='FLAG', action='store_true')
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not args.FLAG:
+        sys.exit("shape_main.py: without --FLAG the reference dumps one PNG per image for inspection; "
+                 "that path is not built here (pass --FLAG to train)")
+    from miscc.shape_losses import check_pcp_lambda
+    check_pcp_lambda(args.PCP_LAMBDA)                   # before any work: no silent fall-back to a loss without the term
+
+    if args.gpu_ids not in ('', '-1'):
+        os.environ.setdefault("CUDA_VISIBLE_DEVICES", args.gpu_ids)
+    import torch
+    from miscc.config import cfg
+    import shapeDataset
+    from shape_trainer import condGANTrainer
+
+    if args.data_dir != '':
+        cfg.DATA_DIR = args.data_dir
+    cfg.TRAIN.NET_G = args.NET_G
+    cfg.TRAIN.MAX_EPOCH = args.MAX_EPOCH
+    cfg.WORKERS = args.WORKERS
+    cfg.TRAIN.DISCRIMINATOR_LR = args.DISCRIMINATOR_LR
+    cfg.TRAIN.GENERATOR_LR = args.GENERATOR_LR
+    cfg.TRAIN.RNN_GRAD_CLIP = 0.25
+    cfg.TRAIN.PRINT_INTERVAL = 5
+    cfg.TRAIN.SMOOTH.INS_LAMBDA = args.INS_LAMBDA
+    cfg.TRAIN.SMOOTH.GLB_LAMBDA = args.GLB_LAMBDA
+    cfg.TRAIN.SMOOTH.PCP_LAMBDA = args.PCP_LAMBDA
+    cfg.GAN.R_NUM = args.R_NUM
+    cfg.TRAIN.BATCH_SIZE = args.BATCH_SIZE
+    cfg.TRAIN.FLAG = True
+    cfg.GPU_IDS = [0]
+    cfg.CUDA = True
+    print('Using config:')
+    pprint.pprint(cfg)
+
+    if args.manualSeed is None:
+        args.manualSeed = random.randint(1, 10000)
+    random.seed(args.manualSeed)
+    np.random.seed(args.manualSeed)
+    torch.manual_seed(args.manualSeed)
+    torch.cuda.manual_seed_all(args.manualSeed)
+
+    timestamp = datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')
+    output_dir = '{0}/output_shape_gen/{1}_{2}'.format(args.output_dir, cfg.DATASET_NAME, timestamp)
+
+    dataset = shapeDataset.TextDataset(cfg.DATA_DIR, 'train', base_size=cfg.TREE.BASE_SIZE)
+    dataloader = torch.utils.data.DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, drop_last=True, shuffle=True,
+                                             num_workers=int(cfg.WORKERS))
+    algo = condGANTrainer(output_dir, dataloader, dataset)
+    start_t = time.time()
+    algo.train()
+    print('Total time for training:', time.time() - start_t)
+    print('Model directory:', algo.model_dir)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,209 @@
+"""Training driver of the shape generator (box layout -> per-box instance masks) on MI355X.
+
+Same entry points as the reference (shape_generation/trainer.py:26-313): `condGANTrainer(output_dir, data_loader,
+dataset)` with `build_models`, `define_optimizers`, `save_model`, `train`; the body of its loop (trainer.py:236-285) is
+`train_step`, usable on its own.  What is built is the adversarial step -- generator, instance and global
+discriminator, gradient clipping, Adam, the EMA copy and the checkpoints.  NOT built: the perceptual (VGG-19) term --
+a non-zero PCP_LAMBDA is refused --, with it `Score/scores_N.txt` (its only content), and the DISPLAY_INTERVAL grids.
+
+Results-preserving differences:
+  * parameters, gradients and Adam moments of each network live in flat arenas (`trainer.ParamArena`): one Adam launch
+    per network, one EMA launch;
+  * `clip_grad_norm_(RNN_GRAD_CLIP)` is `ops.box_train_clip` + the gated Adam: the norm never reaches the host;
+  * the one-hot box maps are written on the device from the compact batch (`shapeDataset.prepare_data`), their maximum
+    over the boxes is taken once per step;
+  * discriminator weights are frozen during the generator step (the reference zeroes those gradients before use);
+  * nothing is read back from the device unless the step prints or a checkpoint is written.
+Kept as it is: the three optimizers are re-created at every epoch (trainer.py:226), so their moments and step counts
+start from zero each epoch; lr_rate *= 0.98 for epochs above 50.
+"""
+import ntpath
+import os
+import time
+
+import torch
+
+from miscc.config import cfg
+from miscc.utils import mkdir_p, weights_init
+from miscc.shape_losses import ins_discriminator_loss, glb_discriminator_loss, generator_loss, check_pcp_lambda
+from model import SHP_G_NET, INS_D_NET, GLB_D_NET
+from trainer import ParamArena, ArenaAdam
+from objgan_hip import ops
+import shapeDataset
+
+EMA_DECAY = 0.999
+
+
+class ClippedArenaAdam(object):
+    """clip_grad_norm_(max_norm) + torch.optim.Adam on a ParamArena with the clip coefficient and the step count on the
+    device: created fresh (zero moments, step 0) like the optimizer it stands for."""
+
+    def __init__(self, arena, lr, max_norm, betas=(0.5, 0.999), eps=1e-8):
+        self.arena, self.lr, self.max_norm, self.betas, self.eps = arena, float(lr), float(max_norm), betas, eps
+        dev = arena.flat.device
+        arena.exp_avg.zero_()
+        arena.exp_avg_sq.zero_()
+        self.state = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
+        self.clip = torch.ones(2, dtype=torch.float32, device=dev)        # divisor, gradient norm
+        self.coef = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.partials = torch.zeros(256, dtype=torch.float64, device=dev)
+
+    def zero_grad(self):
+        self.arena.zero_grad()
+
+    def step(self):
+        a = self.arena
+        if hasattr(ops, "wgrad_join"):
+            ops.wgrad_join()
+        a.sync_grads()
+        a.epoch[0] += 1
+        ops.box_train_clip(a.grad[:a.n], self.max_norm, self.partials, self.clip)
+        ops.adam_step_gated_(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
+                             self.state, self.clip, self.coef, grad_scale=-1.0, n=a.n)
+        ops.repack_arena(a.epoch)
+
+
+def _fresh_adam(arena, lr):
+    """a new torch.optim.Adam in the reference: zero moments, step 0"""
+    arena.exp_avg.zero_()
+    arena.exp_avg_sq.zero_()
+    arena.step_count = 0
+    arena.gate_state = None
+    return ArenaAdam(arena, lr, betas=(0.5, 0.999))
+
+
+def path_leaf(path):
+    head, tail = ntpath.split(path)
+    return tail or ntpath.basename(head)
+
+
+class condGANTrainer(object):
+    def __init__(self, output_dir, data_loader, dataset, device=None):
+        check_pcp_lambda(cfg.TRAIN.SMOOTH.get("PCP_LAMBDA", 0.0))
+        self.model_dir = os.path.join(output_dir, 'Model')
+        if cfg.TRAIN.FLAG:
+            mkdir_p(self.model_dir)
+        self.device = torch.device(device if device is not None else ("cuda:0" if cfg.CUDA else "cpu"))
+        self.batch_size = cfg.TRAIN.BATCH_SIZE
+        self.max_epoch = cfg.TRAIN.MAX_EPOCH
+        self.snapshot_interval = cfg.TRAIN.SNAPSHOT_INTERVAL
+        self.print_interval = cfg.TRAIN.PRINT_INTERVAL
+        self.cats_dict = dataset.cats_dict
+        self.cats_index_dict = dataset.cats_index_dict
+        self.num_classes = len(self.cats_index_dict)
+        self.data_loader = data_loader
+        self.num_batches = len(data_loader) if data_loader is not None else 0
+        self.clip_norm = float(cfg.TRAIN.get("RNN_GRAD_CLIP", 0.25))
+        self.netG = None
+
+    # ---- networks ----
+    def build_models(self):
+        netG, netINSD, netGLBD = SHP_G_NET(self.num_classes), INS_D_NET(self.num_classes), GLB_D_NET(self.num_classes)
+        for net in (netG, netINSD, netGLBD):
+            net.apply(weights_init)
+        epoch = 0
+        if cfg.TRAIN.NET_G != '':
+            netG.load_state_dict(torch.load(cfg.TRAIN.NET_G, map_location="cpu"))
+            print('Load G from: ', cfg.TRAIN.NET_G)
+            name = path_leaf(cfg.TRAIN.NET_G)
+            epoch = int(name[name.rfind('_') + 1:name.rfind('.')]) + 1
+            folder = os.path.dirname(cfg.TRAIN.NET_G)
+            for net, leaf in ((netINSD, 'netINSD.pth'), (netGLBD, 'netGLBD.pth')):
+                print('Load %s from: ' % leaf[3:-4], os.path.join(folder, leaf))
+                net.load_state_dict(torch.load(os.path.join(folder, leaf), map_location="cpu"))
+        self.attach(netG, netINSD, netGLBD)
+        return [netG, netINSD, netGLBD, epoch]
+
+    def attach(self, netG, netINSD, netGLBD):
+        """move the networks to the device and re-home their parameters into flat arenas"""
+        self.netG, self.netINSD, self.netGLBD = (n.to(self.device).train() for n in (netG, netINSD, netGLBD))
+        self.arenaG, self.arenaINSD, self.arenaGLBD = (ParamArena(n) for n in (self.netG, self.netINSD, self.netGLBD))
+        self.avg_param_G = self.arenaG.flat.clone()
+        self.noise = torch.empty(self.batch_size, cfg.ROI.BOXES_NUM, self.num_classes * 4, device=self.device)
+
+    def define_optimizers(self, lr_rate):
+        self.optimizerG = ClippedArenaAdam(self.arenaG, cfg.TRAIN.GENERATOR_LR * lr_rate, self.clip_norm)
+        self.optimizerINSD = _fresh_adam(self.arenaINSD, cfg.TRAIN.DISCRIMINATOR_LR * lr_rate)
+        self.optimizerGLBD = _fresh_adam(self.arenaGLBD, cfg.TRAIN.DISCRIMINATOR_LR * lr_rate)
+        return self.optimizerG, self.optimizerINSD, self.optimizerGLBD
+
+    # ---- one iteration (reference trainer.py:236-285) ----
+    def train_step(self, batch, noise=None):
+        """batch: shapeDataset.prepare_data's dict -> the losses and the generator's gradient norm as device scalars"""
+        R = batch["max_num_roi"]
+        fwd = batch["bbox_maps_fwd"]
+        if noise is None:
+            self.noise.normal_(0, 1)
+            noise = self.noise[:, :R]
+        fake_hmaps = self.netG(noise, fwd, batch["bbox_maps_bwd"], batch["bbox_fmaps"])
+        pooled_maps = ops.box_max(fwd)
+
+        self.optimizerINSD.zero_grad()
+        with ops.direct_wgrad_scope():
+            errINSD = ins_discriminator_loss(self.netINSD, batch["hmaps"], fake_hmaps, fwd)
+            errINSD.backward()
+        self.optimizerINSD.step()
+
+        self.optimizerGLBD.zero_grad()
+        with ops.direct_wgrad_scope():
+            errGLBD = glb_discriminator_loss(self.netGLBD, batch["pooled_hmaps"], fake_hmaps, fwd, pooled_maps)
+            errGLBD.backward()
+        self.optimizerGLBD.step()
+
+        self.optimizerG.zero_grad()
+        self.arenaINSD.set_requires_grad(False)
+        self.arenaGLBD.set_requires_grad(False)
+        try:
+            with ops.direct_wgrad_scope():
+                errG, (insg, glbg) = generator_loss(self.netINSD, self.netGLBD, None, batch["hmaps"], fake_hmaps, fwd,
+                                                    pooled_maps)
+                errG.backward()
+        finally:
+            self.arenaINSD.set_requires_grad(True)
+            self.arenaGLBD.set_requires_grad(True)
+        self.optimizerG.step()
+        ops.ema_update_(self.avg_param_G, self.arenaG.flat, EMA_DECAY)
+        return {"errINSD": errINSD.detach(), "errGLBD": errGLBD.detach(), "errG": errG.detach(),
+                "insg_loss": insg.detach(), "glbg_loss": glbg.detach(), "fake_hmaps": fake_hmaps.detach(),
+                "clip": self.optimizerG.clip}
+
+    # ---- checkpoints ----
+    def save_model(self, epoch):
+        """Model/netG_epoch_N.pth with the EMA weights, netINSD.pth / netGLBD.pth with the live ones"""
+        a = self.arenaG
+        backup = a.flat.clone()
+        a.flat.copy_(self.avg_param_G)
+        try:
+            torch.save({k: v.detach().cpu().clone() for k, v in self.netG.state_dict().items()},
+                       '%s/netG_epoch_%d.pth' % (self.model_dir, epoch))
+        finally:
+            a.flat.copy_(backup)
+        for net, leaf in ((self.netINSD, 'netINSD.pth'), (self.netGLBD, 'netGLBD.pth')):
+            torch.save({k: v.detach().cpu().clone() for k, v in net.state_dict().items()},
+                       '%s/%s' % (self.model_dir, leaf))
+
+    # ---- the loop ----
+    def train(self):
+        start_epoch = self.build_models()[3]
+        print('Not built here: the perceptual loss term (Score/scores_N.txt) and the DISPLAY_INTERVAL image grids.')
+        gen_iterations = 0
+        lr_rate = 1
+        for epoch in range(start_epoch, self.max_epoch):
+            start_t = time.time()
+            if epoch > 50 and lr_rate > cfg.TRAIN.GENERATOR_LR / 10.:
+                lr_rate *= 0.98
+            self.define_optimizers(lr_rate)
+            for step, data in enumerate(self.data_loader, 1):
+                out = self.train_step(shapeDataset.prepare_data(data, self.device, self.num_classes))
+                gen_iterations += 1
+                if gen_iterations % self.print_interval == 0:
+                    vals = {k: float(out[k]) for k in ("errINSD", "errGLBD", "insg_loss", "glbg_loss")}
+                    elapsed = time.time() - start_t
+                    print('| epoch {:3d} | {:5d}/{:5d} batches | ms/batch {:5.2f} | '
+                          .format(epoch, step, self.num_batches, elapsed * 1000. / self.print_interval))
+                    print('errINSD: %.2f \nerrGLBD: %.2f \ninsg_loss: %.2f glbg_loss: %.2f '
+                          % (vals["errINSD"], vals["errGLBD"], vals["insg_loss"], vals["glbg_loss"]))
+                    start_t = time.time()
+            if epoch % self.snapshot_interval == 0:
+                self.save_model(epoch)
+        self.save_model(self.max_epoch)
