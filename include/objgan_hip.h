@@ -519,6 +519,22 @@ int objgan_box_max_backward(const float* dy, const unsigned char* arg, float* dx
 int objgan_boxmaps_onehot(const float* raw, const int* cat, const int* num, float* fwd, float* bwd, int B, int NB, int R,
                           int C, int SS, void* stream);
 
+/* ---- perceptual term of the shape generator's loss (csrc/perceptual.hip) -------------------------
+ * pcp_stem_forward: y[N][3][OH][OW] = (bilinear_align_corners(x[N][1][S][S]) - mean_c) / std_c with the ImageNet
+ *     constants mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225); S == 1 and OH / OW == 1 are scale 0.
+ * pcp_stem_backward: dx[N][1][S][S], gather form, every element written once.
+ * l1_tap_forward: out[slot] = (1 / n) sum |f[i] - r[i]|, fp64 partial sums combined in workgroup order (no atomics);
+ *     ws: objgan_l1_tap_ws_doubles(n) doubles.
+ * l1_tap_backward: g[i] = mask(f[i]) (gdown[i] + coef[0] sign(f[i] - r[i])), sign(0) = 0; gdown NULL: zero;
+ *     relu_mask != 0: mask = f > 0, else 1; coef: ONE float in device memory; amax (may be NULL): the 1024 partial
+ *     maxima of |g| as objgan_act_backward leaves them. */
+int objgan_pcp_stem_forward(const float* x, float* y, int N, int S, int OH, int OW, void* stream);
+int objgan_pcp_stem_backward(const float* dy, float* dx, int N, int S, int OH, int OW, void* stream);
+long objgan_l1_tap_ws_doubles(long n);
+int objgan_l1_tap_forward(const float* f, const float* r, long n, float* out, int slot, double* ws, void* stream);
+int objgan_l1_tap_backward(const float* f, const float* r, const float* gdown, const float* coef, float* g, long n,
+                           int relu_mask, float* amax, void* stream);
+
 /* ---- measurement aid (bench.py roofline leg): hipEvent-bracketed conv launches ------------------ */
 int objgan_prof_enable(int on);
 int objgan_prof_collect(double* ms, double* flops, long* count);   /* arrays of 192 categories (48..95: fp16x2 instances; 96..191: fp16x2 on records, one / two pixel groups) */

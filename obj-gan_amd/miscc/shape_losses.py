@@ -4,7 +4,9 @@ Same three entry points.  Differences, all results-preserving: the mask and the 
 discriminators as the two parts of their first convolution's input (no concatenated tensor), BCE against constant labels
 is one fused kernel (torch's log clamp at -100), the maxima over the box axis are `ops.box_max`.  Padded box slots are
 NOT masked, as in the reference: an image with fewer boxes than the batch maximum still contributes its slots to the
-instance loss and to the maxima.  The perceptual term is not built: `generator_loss` refuses a non-zero PCP_LAMBDA.
+instance loss and to the maxima.  The perceptual term runs the frozen VGG-19-bn (`model.VGG.perceptual`) on the pooled fake
+and real masks in one batch and adds PCP_LAMBDA times the sum of the 19 per-tap L1 means; a non-zero PCP_LAMBDA
+without the network, and a network with PCP_LAMBDA = 0, are refused.
 """
 from miscc.config import cfg
 from objgan_hip import ops
@@ -15,10 +17,15 @@ def _smooth(name, default):
     return float(cfg.TRAIN.SMOOTH.get(name, default))
 
 
-def check_pcp_lambda(value):
-    if float(value) != 0.0:
-        raise ObjganHipError("the perceptual (VGG-19) term of the shape generator's loss is not built yet: "
-                             "PCP_LAMBDA = %g is refused, run with --PCP_LAMBDA 0" % float(value))
+def check_pcp_lambda(value, weights_path=None):
+    """A non-zero PCP_LAMBDA needs the frozen VGG-19-bn: `weights_path` (the torchvision file) must exist.  Called before
+    any work, so that a run never silently trains on a loss without the term."""
+    import os
+    if float(value) != 0.0 and (weights_path is None or not os.path.isfile(weights_path)):
+        raise ObjganHipError("the perceptual (VGG-19-bn) term of the shape generator's loss is not built without its "
+                             "weights file %s: PCP_LAMBDA = %g is refused; put torchvision's vgg19_bn-c79401a0.pth there "
+                             "or run with --PCP_LAMBDA 0" % (weights_path if weights_path is not None else
+                                                             "<DATA_DIR>/pretrained/vgg19_bn-c79401a0.pth", float(value)))
 
 
 def _ins_probs(netINSD, hmaps, bbox_maps):
@@ -50,13 +57,24 @@ def glb_discriminator_loss(netGLBD, real_hmaps, fake_hmaps, bbox_maps, pooled_ma
 
 
 def generator_loss(netINSD, netGLBD, vgg_model, real_hmaps, fake_hmaps, bbox_maps, pooled_maps=None):
-    """-> (errG_total, (insg_loss, glbg_loss)): device scalars, formatted by the caller only when it prints.
-    vgg_model is the reference's argument slot for the perceptual network: it must be None."""
-    check_pcp_lambda(_smooth("PCP_LAMBDA", 0.0))
-    if vgg_model is not None:
-        raise ObjganHipError("generator_loss: the perceptual term is not built yet, pass vgg_model=None")
+    """vgg_model None and PCP_LAMBDA == 0 -> (errG_total, (insg_loss, glbg_loss)); with the frozen network (model.VGG)
+    and PCP_LAMBDA != 0 -> (errG_total, (insg_loss, glbg_loss, gpcp_loss), pcp_score) where gpcp_loss = PCP_LAMBDA *
+    sum_i mean |fake_i - real_i| over the 19 taps and pcp_score is the unweighted sum (the reference's item_pcp_score).
+    Device scalars, formatted by the caller only when it prints.  real_hmaps [B, R, 1, S, S]."""
+    lam = _smooth("PCP_LAMBDA", 0.0)
+    if lam != 0.0 and vgg_model is None:
+        raise ObjganHipError("generator_loss: PCP_LAMBDA = %g needs the frozen VGG-19-bn (vgg_model is None); there is no "
+                             "silent loss without the term" % lam)
+    if lam == 0.0 and vgg_model is not None:
+        raise ObjganHipError("generator_loss: a perceptual network was passed but PCP_LAMBDA is 0: pass vgg_model=None")
     insg_loss = ops.bce_const(_ins_probs(netINSD, fake_hmaps, bbox_maps), 1.0) * _smooth("INS_LAMBDA", 1.0)
     if pooled_maps is None:
         pooled_maps = ops.box_max(bbox_maps.detach())
-    glbg_loss = ops.bce_const(_glb_probs(netGLBD, ops.box_max(fake_hmaps), pooled_maps), 1.0) * _smooth("GLB_LAMBDA", 1.0)
-    return insg_loss + glbg_loss, (insg_loss, glbg_loss)
+    fake_pooled = ops.box_max(fake_hmaps)
+    glbg_loss = ops.bce_const(_glb_probs(netGLBD, fake_pooled, pooled_maps), 1.0) * _smooth("GLB_LAMBDA", 1.0)
+    if vgg_model is None:
+        return insg_loss + glbg_loss, (insg_loss, glbg_loss)
+    taps = vgg_model.perceptual(fake_pooled, ops.box_max(real_hmaps.detach()))
+    pcp_score = taps.sum()
+    gpcp_loss = pcp_score * lam
+    return insg_loss + glbg_loss + gpcp_loss, (insg_loss, glbg_loss, gpcp_loss), pcp_score.detach()

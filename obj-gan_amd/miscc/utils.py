@@ -410,6 +410,18 @@ def form_hmaps(raw_masks, num_rois, rois, hmap_size, num_classes):
     return gen_hmaps, gen_bt_masks, gen_fm_bt_masks
 
 
+VGG_PIXEL_MEANS = (0.485, 0.456, 0.406)
+VGG_PIXEL_STDS = (0.229, 0.224, 0.225)
+
+
+def vgg_norm(input):
+    """(input - mean_c) / std_c of a [batch, 3, h, w] tensor (reference shape_generation/miscc/utils.py:351-365).  Plain
+    torch, for API parity: the training path normalises inside `ops.pcp_stem_forward`."""
+    means = torch.tensor(VGG_PIXEL_MEANS, dtype=input.dtype, device=input.device).view(1, -1, 1, 1)
+    stds = torch.tensor(VGG_PIXEL_STDS, dtype=input.dtype, device=input.device).view(1, -1, 1, 1)
+    return (input - means) / stds
+
+
 # ---- FID (reference utils.py:358-362, 586-714) ---------------------------------------------------
 def denorm_imgs(images):
     """[-1, 1] float images -> uint8 [0, 255] numpy array (reference utils.py:358-362)."""

@@ -31,6 +31,7 @@ from GlobalAttention import GlobalAttentionGeneral as ATT_NET
 from GlobalAttention import GlobalBUAttentionGeneral as BT_ATT_NET
 from models.roi_align.modules.roi_align import RoIAlignAvg
 from objgan_hip import ops
+from objgan_hip._lib import ObjganHipError
 
 
 # ---------------------------------------------------------------------------------------------
@@ -907,3 +908,185 @@ class OBJ_SS_D_NET(_ObjD):
 
 class OBJ_LS_D_NET(_ObjD):
     n_layer = 4
+
+
+# ---------------------------------------------------------------------------------------------
+# frozen VGG-19-bn of the shape generator's perceptual term (reference shape_generation/model.py:279-360)
+# ---------------------------------------------------------------------------------------------
+vgg_cfg = {'E': [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M']}
+VGG_INPUT = 224
+VGG_BN_EPS = 1e-5
+VGG_WEIGHTS_FILE = 'vgg19_bn-c79401a0.pth'
+
+
+def vgg_plan(state_dict):
+    """The network a torchvision-style VGG-bn state dict describes: every dimension is read off its tensors.
+    -> [("conv", features index) | ("pool",) | ("fc", classifier index, relu)] in network order.
+    Pools carry no parameters: between two convolutions their number is the gap in the `features` indices (conv,
+    norm, ReLU take three, a pool one); behind the last convolution it follows from the first Linear's input width,
+    C_last * (224 / 2^pools)^2 with x.view(N, -1) in NCHW order."""
+    convs = sorted(int(k.split('.')[1]) for k, v in state_dict.items()
+                   if k.startswith('features.') and k.endswith('.weight') and v.dim() == 4)
+    fcs = sorted(int(k.split('.')[1]) for k, v in state_dict.items()
+                 if k.startswith('classifier.') and k.endswith('.weight') and v.dim() == 2)
+    if not convs or not fcs:
+        raise ObjganHipError("vgg19_bn: the state dict has no features.N.weight / classifier.N.weight tensors")
+    plan, pools, cin = [], 0, 3
+    for pos, i in enumerate(convs):
+        w = state_dict['features.%d.weight' % i]
+        for suffix in ('weight', 'bias', 'running_mean', 'running_var'):
+            key = 'features.%d.%s' % (i + 1, suffix)
+            if key not in state_dict or tuple(state_dict[key].shape) != (w.shape[0],):
+                raise ObjganHipError("vgg19_bn: %s (BatchNorm of features.%d, %d channels) is missing or misshapen"
+                                     % (key, i, w.shape[0]))
+        if tuple(w.shape[1:]) != (cin, 3, 3) or 'features.%d.bias' % i not in state_dict:
+            raise ObjganHipError("vgg19_bn: features.%d.weight is %s, expected [*, %d, 3, 3] with a bias"
+                                 % (i, tuple(w.shape), cin))
+        plan.append(("conv", i))
+        cin = w.shape[0]
+        if pos + 1 < len(convs):
+            gap = convs[pos + 1] - i - 3
+            if gap < 0:
+                raise ObjganHipError("vgg19_bn: features.%d and features.%d are too close for conv, norm, ReLU"
+                                     % (i, convs[pos + 1]))
+            plan += [("pool",)] * gap
+            pools += gap
+    fc_in = state_dict['classifier.%d.weight' % fcs[0]].shape[1]
+    side, tail = VGG_INPUT >> pools, None
+    for extra in range(0, 9):
+        if side >> extra >= 1 and cin * (side >> extra) ** 2 == fc_in:
+            tail = extra
+            break
+    if tail is None:
+        raise ObjganHipError("vgg19_bn: classifier.%d.weight takes %d inputs; no pool count maps %d channels of a "
+                             "%d x %d map onto it" % (fcs[0], fc_in, cin, side, side))
+    plan += [("pool",)] * tail
+    width = fc_in
+    for pos, i in enumerate(fcs):
+        w = state_dict['classifier.%d.weight' % i]
+        if w.shape[1] != width or 'classifier.%d.bias' % i not in state_dict:
+            raise ObjganHipError("vgg19_bn: classifier.%d.weight is %s, expected [*, %d] with a bias" % (i, tuple(w.shape), width))
+        plan.append(("fc", i, pos + 1 < len(fcs)))          # (the last Linear is tapped raw)
+        width = w.shape[0]
+    return plan
+
+
+def vgg_fold(state_dict, plan=None):
+    """Eval-mode BatchNorm folded into each convolution, in fp64, rounded to fp32 once:
+    w' = w g / sqrt(var + eps), b' = (b - mean) g / sqrt(var + eps) + beta.
+    -> [("conv", w', b') | ("pool",) | ("fc", w [Cout, Cin, 1, 1], b, relu)] (CPU tensors)"""
+    plan = vgg_plan(state_dict) if plan is None else plan
+    layers = []
+    for item in plan:
+        if item[0] == "conv":
+            i = item[1]
+            w, b = (state_dict['features.%d.%s' % (i, s)].detach().double() for s in ('weight', 'bias'))
+            g, beta, mean, var = (state_dict['features.%d.%s' % (i + 1, s)].detach().double()
+                                  for s in ('weight', 'bias', 'running_mean', 'running_var'))
+            k = g / torch.sqrt(var + VGG_BN_EPS)
+            layers.append(("conv", (w * k.view(-1, 1, 1, 1)).float().contiguous(), ((b - mean) * k + beta).float().contiguous()))
+        elif item[0] == "fc":
+            w, b = (state_dict['classifier.%d.%s' % (item[1], s)].detach().float() for s in ('weight', 'bias'))
+            layers.append(("fc", w.reshape(w.shape[0], w.shape[1], 1, 1).contiguous().clone(), b.contiguous().clone(), item[2]))
+        else:
+            layers.append(("pool",))
+    return layers
+
+
+def vgg_init_state(widths=None, classifier=(4096, 4096, 1000)):
+    """a freshly initialised state dict in torchvision's layout (reference VGG._initialize_weights)"""
+    widths = vgg_cfg['E'] if widths is None else widths
+    sd, idx, cin = {}, 0, 3
+    for v in widths:
+        if v == 'M':
+            idx += 1
+            continue
+        sd['features.%d.weight' % idx] = torch.randn(v, cin, 3, 3) * (2.0 / (v * 9)) ** 0.5       # kaiming, fan_out
+        sd['features.%d.bias' % idx] = torch.zeros(v)
+        sd['features.%d.weight' % (idx + 1)] = torch.ones(v)
+        sd['features.%d.bias' % (idx + 1)] = torch.zeros(v)
+        sd['features.%d.running_mean' % (idx + 1)] = torch.zeros(v)
+        sd['features.%d.running_var' % (idx + 1)] = torch.ones(v)
+        sd['features.%d.num_batches_tracked' % (idx + 1)] = torch.zeros((), dtype=torch.long)
+        idx, cin = idx + 3, v
+    side = VGG_INPUT >> sum(1 for v in widths if v == 'M')
+    width = cin * side * side
+    for j, out in zip((0, 3, 6), classifier):
+        sd['classifier.%d.weight' % j] = torch.randn(out, width) * 0.01
+        sd['classifier.%d.bias' % j] = torch.zeros(out)
+        width = out
+    return sd
+
+
+class VGG(nn.Module):
+    """Frozen VGG-bn feature network: the folded banks are buffers (never parameters), every layer is one MFMA
+    implicit-GEMM launch with bias and ReLU in its epilogue, the Linears are 1x1 convolutions over [N, C, 1, 1].
+    `forward(x)` is the reference's (19 features of a normalised 3-channel input, forward only); the training path
+    is `perceptual(fake_pooled, real_pooled)`."""
+
+    def __init__(self, state_dict):
+        super(VGG, self).__init__()
+        self.plan = vgg_plan(state_dict)
+        self._kinds = []
+        for n, layer in enumerate(vgg_fold(state_dict, self.plan)):
+            self._kinds.append((layer[0], layer[3] if layer[0] == "fc" else None))
+            if layer[0] != "pool":
+                self.register_buffer("w%d" % n, layer[1], persistent=False)
+                self.register_buffer("b%d" % n, layer[2], persistent=False)
+        self.num_taps = sum(1 for k in self._kinds if k[0] != "pool")
+        self._layers_for = None
+        self.eval()
+
+    def train(self, mode=True):
+        return super(VGG, self).train(False)                # frozen: always eval
+
+    def layers(self):
+        dev = self.w0.device
+        if self._layers_for is None or self._layers_for[0] != (dev, self.w0.data_ptr()):
+            out = []
+            for n, (kind, relu) in enumerate(self._kinds):
+                if kind == "pool":
+                    out.append(("pool",))
+                elif kind == "conv":
+                    out.append(("conv", getattr(self, "w%d" % n), getattr(self, "b%d" % n)))
+                else:
+                    out.append(("fc", getattr(self, "w%d" % n), getattr(self, "b%d" % n), relu))
+            self._layers_for = ((dev, self.w0.data_ptr()), out)
+        return self._layers_for[1]
+
+    def forward(self, x):
+        results = []
+        with torch.no_grad():
+            x = ops.bilinear_resize(x, VGG_INPUT, VGG_INPUT)
+            for layer in self.layers():
+                if layer[0] == "pool":
+                    x = ops.max_pool2d(x, 2, 2)
+                    continue
+                if layer[0] == "conv":
+                    x = ops.conv2d_frozen(x, layer[1], layer[2], 1, (1, 1), "relu")
+                else:
+                    x = ops.conv2d_frozen(x.reshape(x.shape[0], -1, 1, 1), layer[1], layer[2], 1, (0, 0),
+                                          "relu" if layer[3] else None)
+                results.append(x.reshape(x.shape[0], -1) if layer[0] == "fc" else x)
+        return results
+
+    def perceptual(self, fake_pooled, real_pooled):
+        """fake_pooled, real_pooled [B, 1, S, S] (maxima over the boxes) -> the per-tap means of |fake_i - real_i|
+        [19]; their sum is the reference's item_pcp_score.  Differentiable w.r.t. fake_pooled only."""
+        return ops.perceptual_taps(fake_pooled, real_pooled, self.layers())
+
+
+def vgg_weights_path(data_dir=None):
+    import os
+    return os.path.join(cfg.DATA_DIR if data_dir is None else data_dir, 'pretrained', VGG_WEIGHTS_FILE)
+
+
+def vgg19_bn(pretrained=False, state_dict=None, **kwargs):
+    """VGG 19-layer model (configuration 'E') with batch normalization, frozen.  pretrained: the torchvision weights
+    from <DATA_DIR>/pretrained/vgg19_bn-c79401a0.pth; state_dict: any state dict in that layout (thin test networks)."""
+    if state_dict is None:
+        if pretrained:
+            state_dict = torch.load(vgg_weights_path(), map_location="cpu")
+        else:
+            state_dict = vgg_init_state()
+    return VGG(state_dict)

@@ -102,6 +102,10 @@ SIGNATURES = {
     "objgan_box_max_forward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
     "objgan_box_max_backward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
     "objgan_boxmaps_onehot": [_ptr] * 5 + [_c_int] * 5 + [_ptr],
+    "objgan_pcp_stem_forward": [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr],
+    "objgan_pcp_stem_backward": [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr],
+    "objgan_l1_tap_forward": [_ptr, _ptr, _c_long, _ptr, _c_int, _ptr, _ptr],
+    "objgan_l1_tap_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _c_long, _c_int, _ptr, _ptr],
     "objgan_prof_enable": [_c_int],
     "objgan_conv_bank_layout": [_c_int] * 10,
     "objgan_conv_wgrad_rec_ok": [_c_int] * 8,
@@ -126,6 +130,7 @@ LONG_RETURN = {"objgan_conv_packed_floats": [_c_int, _c_int, _c_int],
                "objgan_attn_general_backward_ws_floats": [_c_int] * 4,
                "objgan_masked_max_backward_ws_floats": [_c_int] * 4,
                "objgan_channel_sum_ws_floats": [_c_int] * 3,
+               "objgan_l1_tap_ws_doubles": [_c_long],
                "objgan_roi_align_backward_ws_floats": [_c_int] * 7,
                "objgan_snapshot_ws_doubles": [_c_int] * 4,
                "objgan_jpeg_desc_bytes": [],

@@ -1111,6 +1111,60 @@ def conv2d(x, w, bias=None, stride=1, pad=0, pad_mode="zeros", upsample=False, a
     return _Conv2dFn.apply(x, w, bias, stride, pad, pad_mode, upsample, act)
 
 
+def _frozen_fwd(x, w, bias, stride, ph, pw, act):
+    """y = act(conv(x, w) + bias) with a frozen rectangular bank, no tape"""
+    N, Cin, H, W = x.shape
+    Cout, Cin2, KH, KW = w.shape
+    if Cin2 != Cin or KH * KW > 32:
+        raise _lib.ObjganHipError("conv2d_frozen: unsupported filter %s" % (tuple(w.shape),))
+    OH = (H + 2 * ph - KH) // stride + 1
+    OW = (W + 2 * pw - KW) // stride + 1
+    y = torch.empty((N, Cout, OH, OW), dtype=_F32, device=x.device)
+    dh = [kh - ph for kh in range(KH) for kw in range(KW)]
+    dw = [kw - pw for kh in range(KH) for kw in range(KW)]
+    # (the frozen encoder's convolutions feed each other through a fused ReLU: the epilogue leaves the maxima)
+    ym = _amax_zeroed(x.device) if (act in ("lrelu", "relu") and _amax_wanted(y.numel())) else None
+    _igemm(x, w, bias, y, N, Cin, H, W, 0, 0, Cout, Cin, KH * KW, 0, dh, dw, list(range(KH * KW)),
+           OH, OW, stride, OH, OW, 1, 1, 0, 0, _ACT[act], ymax=ym)
+    if ym is not None:
+        _amax_attach(y, ym)
+    return y
+
+
+def _frozen_dgrad(g, w, stride, ph, pw, N, Cin, H, W):
+    """gradient w.r.t. the input [N, Cin, H, W] of a frozen convolution given g = dL/d(its pre-activation output)"""
+    Cout, KH, KW = w.shape[0], w.shape[2], w.shape[3]
+    OH, OW = g.shape[2], g.shape[3]
+    T = KH * KW
+    if stride == 1:
+        dx = torch.empty((N, Cin, H, W), dtype=_F32, device=g.device)
+        dh = [ph - kh for kh in range(KH) for kw in range(KW)]
+        dw = [pw - kw for kh in range(KH) for kw in range(KW)]
+        _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, list(range(T)),
+               H, W, 1, H, W, 1, 1, 0, 0, 0)
+    elif stride == 2:
+        dx = _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, (KH, KW), ph, pw, H, W)
+        phases = range(2) if dx is None else ()
+        if dx is None:
+            dx = torch.zeros((N, Cin, H, W), dtype=_F32, device=g.device)
+        for a in phases:
+            khs = [kh for kh in range(KH) if (a + ph - kh) % 2 == 0]
+            PHg = (H - a + 1) // 2
+            for b in range(2):
+                kws = [kw for kw in range(KW) if (b + pw - kw) % 2 == 0]
+                PWg = (W - b + 1) // 2
+                if PHg <= 0 or PWg <= 0 or not khs or not kws:
+                    continue
+                dh = [(a + ph - kh) // 2 for kh in khs for kw in kws]
+                dw = [(b + pw - kw) // 2 for kh in khs for kw in kws]
+                st = [kh * KW + kw for kh in khs for kw in kws]
+                _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, st,
+                       PHg, PWg, 1, H, W, 2, 2, a, b, 0, y_prezeroed=1)
+    else:
+        raise _lib.ObjganHipError("conv2d_frozen backward: stride %d not supported" % stride)
+    return dx
+
+
 class _ConvFrozenFn(torch.autograd.Function):
     """Convolution with a FROZEN (non-trainable) rectangular filter bank: forward + input gradient
     only.  Serves the frozen Inception-v3 encoder (1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1 kernels,
@@ -1122,34 +1176,18 @@ class _ConvFrozenFn(torch.autograd.Function):
         if w.requires_grad or (bias is not None and bias.requires_grad):
             raise _lib.ObjganHipError("conv2d_frozen: the filter bank must not require gradients")
         x, w = _c(x), _c(w)
-        N, Cin, H, W = x.shape
-        Cout, Cin2, KH, KW = w.shape
-        if Cin2 != Cin or KH * KW > 32:
-            raise _lib.ObjganHipError("conv2d_frozen: unsupported filter %s" % (tuple(w.shape),))
-        OH = (H + 2 * ph - KH) // stride + 1
-        OW = (W + 2 * pw - KW) // stride + 1
-        y = torch.empty((N, Cout, OH, OW), dtype=_F32, device=x.device)
-        dh = [kh - ph for kh in range(KH) for kw in range(KW)]
-        dw = [kw - pw for kh in range(KH) for kw in range(KW)]
-        # (the frozen encoder's convolutions feed each other through a fused ReLU: the epilogue leaves the maxima)
-        ym = _amax_zeroed(x.device) if (act in ("lrelu", "relu") and _amax_wanted(y.numel())) else None
-        _igemm(x, w, bias, y, N, Cin, H, W, 0, 0, Cout, Cin, KH * KW, 0, dh, dw, list(range(KH * KW)),
-               OH, OW, stride, OH, OW, 1, 1, 0, 0, _ACT[act], ymax=ym)
-        if ym is not None:
-            _amax_attach(y, ym)
-        ctx.cfg = (stride, ph, pw, act, KH, KW, (N, Cin, H, W))
+        y = _frozen_fwd(x, w, bias, stride, ph, pw, act)
+        ctx.cfg = (stride, ph, pw, act, tuple(x.shape))
         ctx.save_for_backward(w, y if act not in (None, "none") else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         w, y = ctx.saved_tensors
-        stride, ph, pw, act, KH, KW, (N, Cin, H, W) = ctx.cfg
+        stride, ph, pw, act, (N, Cin, H, W) = ctx.cfg
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None, None
-        Cout = w.shape[0]
         dy = _c(dy)
-        OH, OW = dy.shape[2], dy.shape[3]
         if act not in (None, "none"):
             g = torch.empty_like(dy)
             am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=dy.device) if _amax_wanted(dy.numel()) else None
@@ -1158,34 +1196,7 @@ class _ConvFrozenFn(torch.autograd.Function):
                 _amax_attach(g, am)
         else:
             g = dy
-        T = KH * KW
-        if stride == 1:
-            dx = torch.empty((N, Cin, H, W), dtype=_F32, device=dy.device)
-            dh = [ph - kh for kh in range(KH) for kw in range(KW)]
-            dw = [pw - kw for kh in range(KH) for kw in range(KW)]
-            _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, list(range(T)),
-                   H, W, 1, H, W, 1, 1, 0, 0, 0)
-        elif stride == 2:
-            dx = _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, (KH, KW), ph, pw, H, W)
-            phases = range(2) if dx is None else ()
-            if dx is None:
-                dx = torch.zeros((N, Cin, H, W), dtype=_F32, device=dy.device)
-            for a in phases:
-                khs = [kh for kh in range(KH) if (a + ph - kh) % 2 == 0]
-                PHg = (H - a + 1) // 2
-                for b in range(2):
-                    kws = [kw for kw in range(KW) if (b + pw - kw) % 2 == 0]
-                    PWg = (W - b + 1) // 2
-                    if PHg <= 0 or PWg <= 0 or not khs or not kws:
-                        continue
-                    dh = [(a + ph - kh) // 2 for kh in khs for kw in kws]
-                    dw = [(b + pw - kw) // 2 for kh in khs for kw in kws]
-                    st = [kh * KW + kw for kh in khs for kw in kws]
-                    _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, st,
-                           PHg, PWg, 1, H, W, 2, 2, a, b, 0, y_prezeroed=1)
-        else:
-            raise _lib.ObjganHipError("conv2d_frozen backward: stride %d not supported" % stride)
-        return dx, None, None, None, None, None, None
+        return _frozen_dgrad(g, w, stride, ph, pw, N, Cin, H, W), None, None, None, None, None, None
 
 
 def conv2d_frozen(x, w, bias=None, stride=1, pad=(0, 0), act=None):
@@ -2553,3 +2564,150 @@ def boxmaps_onehot(raw, cats, num_rois, R, C):
     _lib.call("objgan_boxmaps_onehot", _p(raw), _p(_c(cats)), _p(_c(num_rois)), _p(fwd), _p(bwd), B, NB, int(R), int(C),
               S1 * S2, _stream())
     return fwd, bwd
+
+
+# ----------------------------------------------------------------------------------------------
+# perceptual term of the shape generator's loss (csrc/perceptual.hip)
+# ----------------------------------------------------------------------------------------------
+PCP_SIZE = 224          # the frozen network's input side (reference shape_generation/model.py:301)
+
+
+def pcp_stem_forward(x, oh=PCP_SIZE, ow=None):
+    """x [N, 1, S, S] -> (bilinear_align_corners(x) - mean_c) / std_c as [N, 3, oh, ow]; no tape"""
+    _chk(x)
+    x = _c(x)
+    ow = oh if ow is None else ow
+    N, S = x.shape[0], x.shape[-1]
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != S:
+        raise _lib.ObjganHipError("pcp_stem_forward: x is [N, 1, S, S] (got %s)" % (tuple(x.shape),))
+    y = torch.empty((N, 3, int(oh), int(ow)), dtype=_F32, device=x.device)
+    _lib.call("objgan_pcp_stem_forward", _p(x), _p(y), N, S, int(oh), int(ow), _stream())
+    return y
+
+
+def pcp_stem_backward(dy, S):
+    """dy [N, 3, OH, OW] -> dx [N, 1, S, S]"""
+    _chk(dy)
+    dy = _c(dy)
+    N = dy.shape[0]
+    dx = torch.empty((N, 1, int(S), int(S)), dtype=_F32, device=dy.device)
+    _lib.call("objgan_pcp_stem_backward", _p(dy), _p(dx), N, int(S), dy.shape[2], dy.shape[3], _stream())
+    return dx
+
+
+def _flat_view(t, what):
+    if not t.is_contiguous():
+        raise _lib.ObjganHipError("%s: contiguous tensors only" % what)
+    return t
+
+
+def l1_tap_forward(f, r, out, slot, ws=None):
+    """out[slot] = mean |f - r| (f, r: the two halves of one tap); ws: reusable fp64 workspace"""
+    _chk(f, r, out)
+    _flat_view(f, "l1_tap_forward"), _flat_view(r, "l1_tap_forward")
+    n = f.numel()
+    if r.numel() != n or n == 0 or not 0 <= slot < out.numel():
+        raise _lib.ObjganHipError("l1_tap_forward: two halves of equal, non-zero size and a slot inside `out`")
+    need = _q("objgan_l1_tap_ws_doubles", n)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.float64, device=f.device)
+    _lib.call("objgan_l1_tap_forward", _p(f), _p(r), n, _p(out), int(slot), _p(ws), _stream())
+    return out
+
+
+def l1_tap_backward(f, r, gdown, coef, relu_mask, want_amax=None):
+    """g = mask(f) * (gdown + coef * sign(f - r)); coef: a one-element device tensor; gdown None at the deepest tap.
+    The partial maxima of |g| are attached to g when an fp16x2 launch could read it."""
+    _chk(f, r, gdown, coef)
+    _flat_view(f, "l1_tap_backward"), _flat_view(r, "l1_tap_backward")
+    n = f.numel()
+    if r.numel() != n or n == 0 or coef.numel() != 1 or (gdown is not None and (gdown.numel() != n or not gdown.is_contiguous())):
+        raise _lib.ObjganHipError("l1_tap_backward: f, r and gdown of equal, non-zero size; coef one float")
+    g = torch.empty_like(f)
+    want = _amax_wanted(n) if want_amax is None else want_amax
+    am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=f.device) if want else None
+    _lib.call("objgan_l1_tap_backward", _p(f), _p(r), _p(gdown), _p(coef), _p(g), n, int(bool(relu_mask)), _p(am), _stream())
+    if am is not None:
+        _amax_attach(g, am)
+    return (g, am) if want_amax else g
+
+
+class _PerceptualFn(torch.autograd.Function):
+    """The frozen VGG-19-bn of the perceptual term on [fake; real] in one batch, and the 19 per-tap L1 means.
+    `layers`: ("conv", w [Cout, Cin, 3, 3], b) with batch norm folded in, ("pool",), ("fc", w [Cout, Cin, 1, 1], b, relu)
+    in network order.  The backward walks the chain by hand on the fake half: tap gradient (L1 + what arrives from below
+    + ReLU mask, one pass), data gradient, pool gather; no weight gradient, nothing for the real half."""
+
+    @staticmethod
+    def forward(ctx, fake_pooled, real_pooled, layers):
+        _chk(fake_pooled, real_pooled)
+        if fake_pooled.shape != real_pooled.shape:
+            raise _lib.ObjganHipError("perceptual: fake and real pooled maps differ in shape")
+        B, S = fake_pooled.shape[0], fake_pooled.shape[-1]
+        x = pcp_stem_forward(torch.cat((fake_pooled.detach(), real_pooled.detach()), 0))
+        ntaps = sum(1 for l in layers if l[0] != "pool")
+        means = torch.empty(ntaps, dtype=_F32, device=x.device)
+        ws = None                                     # one fp64 workspace for all taps (stream-ordered reuse)
+        need = ctx.needs_input_grad[0]
+        trail = []                                    # per layer: (kind, input shape, tap | pool indices)
+        slot = 0
+        for layer in layers:
+            kind = layer[0]
+            if kind == "pool":
+                N2, C, H, W = x.shape
+                OH, OW = H // 2, W // 2
+                y = torch.empty((N2, C, OH, OW), dtype=_F32, device=x.device)
+                idx = torch.empty(y.shape, dtype=torch.int32, device=x.device) if need else None
+                _lib.call("objgan_pool2d_forward", _p(x), _p(y), _p(idx), N2 * C, H, W, OH, OW, 2, 2, 0, 0, _stream())
+                trail.append((kind, tuple(x.shape), idx))
+                x = y
+                continue
+            if kind == "fc" and x.dim() == 4 and x.shape[2] * x.shape[3] != 1:
+                x = x.reshape(x.shape[0], -1, 1, 1)                   # x.view(N, -1): NCHW order
+            shape_in = tuple(x.shape)
+            if kind == "conv":
+                y = _frozen_fwd(x, layer[1], layer[2], 1, 1, 1, "relu")
+            else:
+                y = _frozen_fwd(x, layer[1], layer[2], 1, 0, 0, "relu" if layer[3] else None)
+            need = _q("objgan_l1_tap_ws_doubles", y[:B].numel())
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.float64, device=x.device)
+            l1_tap_forward(y[:B], y[B:], means, slot, ws)
+            slot += 1
+            trail.append((kind, shape_in, y if need else None))
+            x = y
+        ctx.trail, ctx.layers, ctx.B, ctx.S = trail, layers, B, S
+        return means
+
+    @staticmethod
+    def backward(ctx, dmeans):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        B, layers, trail = ctx.B, ctx.layers, ctx.trail
+        dmeans = _c(dmeans)
+        counts = torch.tensor([float(t[2][:B].numel()) for t in trail if t[0] != "pool"], dtype=torch.float64,
+                              device=dmeans.device)
+        coefs = (dmeans.double() / counts).float()                    # upstream * lambda / n per tap, on the device
+        slot = coefs.numel()
+        g = None                                                      # gradient w.r.t. the current layer's OUTPUT (fake half)
+        for layer, (kind, shape_in, kept) in zip(reversed(layers), reversed(trail)):
+            if kind == "pool":
+                N2, C, H, W = shape_in
+                dx = torch.empty((B, C, H, W), dtype=_F32, device=g.device)
+                g = _c(g.reshape(B, C, H // 2, W // 2))
+                _lib.call("objgan_pool2d_backward", _p(g), _p(kept[:B]), _p(dx), B * C, H, W, H // 2, W // 2, 2, 2, 0, 0,
+                          _stream())
+                g = dx
+                continue
+            slot -= 1
+            f, r = kept[:B], kept[B:]
+            relu = kind == "conv" or layer[3]
+            g = l1_tap_backward(f, r, None if g is None else _c(g.reshape(f.shape)), coefs[slot:slot + 1], relu)
+            pad = 1 if kind == "conv" else 0
+            g = _frozen_dgrad(g, layer[1], 1, pad, pad, B, shape_in[1], shape_in[2], shape_in[3])
+        return pcp_stem_backward(g, ctx.S), None, None
+
+
+def perceptual_taps(fake_pooled, real_pooled, layers):
+    """-> the per-tap means of |fake_i - real_i| [number of taps]; differentiable w.r.t. fake_pooled only"""
+    return _PerceptualFn.apply(fake_pooled, real_pooled, layers)

@@ -1,11 +1,12 @@
 """Command line of the shape generator's training: the reference's `shape_generation/main.py --FLAG` (main.py:24-111).
 
-    python shape_main.py --FLAG --PCP_LAMBDA 0 --data_dir ../data/coco --output_dir ..
+    python shape_main.py --FLAG --data_dir ../data/coco --output_dir ..
 
-Same arguments.  Refused, loudly: a non-zero --PCP_LAMBDA (the perceptual VGG-19 term is not built yet; the reference's
-default of 10 therefore has to be overridden with `--PCP_LAMBDA 0`) and a run without --FLAG (the reference's
+Same arguments, same defaults (--PCP_LAMBDA 10: the perceptual term on the frozen VGG-19-bn, whose torchvision weights
+are read from <data_dir>/pretrained/vgg19_bn-c79401a0.pth).  Refused, loudly: a non-zero --PCP_LAMBDA when that file is
+missing (before any work; `--PCP_LAMBDA 0` trains without the term) and a run without --FLAG (the reference's
 single-PNG inspection dump is not built).  The run happens on the GPU: `--gpu` names the device (default 0; the
-reference's `-1` CPU mode does not exist here).
+reference's `-1` CPU mode does not exist here).  Written: Model/ (checkpoints) and Score/scores_<epoch>.txt.
 """
 import argparse
 import datetime
@@ -44,7 +45,8 @@ def main(argv=None):
         sys.exit("shape_main.py: without --FLAG the reference dumps one PNG per image for inspection; "
                  "that path is not built here (pass --FLAG to train)")
     from miscc.shape_losses import check_pcp_lambda
-    check_pcp_lambda(args.PCP_LAMBDA)                   # before any work: no silent fall-back to a loss without the term
+    # before any work: no silent fall-back to a loss without the term
+    check_pcp_lambda(args.PCP_LAMBDA, os.path.join(args.data_dir, 'pretrained', 'vgg19_bn-c79401a0.pth'))
 
     if args.gpu_ids not in ('', '-1'):
         os.environ.setdefault("CUDA_VISIBLE_DEVICES", args.gpu_ids)

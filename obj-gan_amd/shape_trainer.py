@@ -2,9 +2,10 @@
 
 Same entry points as the reference (shape_generation/trainer.py:26-313): `condGANTrainer(output_dir, data_loader,
 dataset)` with `build_models`, `define_optimizers`, `save_model`, `train`; the body of its loop (trainer.py:236-285) is
-`train_step`, usable on its own.  What is built is the adversarial step -- generator, instance and global
-discriminator, gradient clipping, Adam, the EMA copy and the checkpoints.  NOT built: the perceptual (VGG-19) term --
-a non-zero PCP_LAMBDA is refused --, with it `Score/scores_N.txt` (its only content), and the DISPLAY_INTERVAL grids.
+`train_step`, usable on its own.  What is built is the whole step -- generator, instance and global discriminator, the
+perceptual term on the frozen VGG-19-bn (PCP_LAMBDA != 0: the network is loaded once from
+<DATA_DIR>/pretrained/vgg19_bn-c79401a0.pth, a missing file is refused before any work), gradient clipping, Adam, the
+EMA copy, the checkpoints and `Score/scores_N.txt`.  NOT built: the DISPLAY_INTERVAL grids.
 
 Results-preserving differences:
   * parameters, gradients and Adam moments of each network live in flat arenas (`trainer.ParamArena`): one Adam launch
@@ -13,7 +14,8 @@ Results-preserving differences:
   * the one-hot box maps are written on the device from the compact batch (`shapeDataset.prepare_data`), their maximum
     over the boxes is taken once per step;
   * discriminator weights are frozen during the generator step (the reference zeroes those gradients before use);
-  * nothing is read back from the device unless the step prints or a checkpoint is written.
+  * nothing is read back from the device unless the step prints or a checkpoint is written; pcp_score accumulates on
+    the device and is read once per epoch (it is never reset between epochs, as in the reference).
 Kept as it is: the three optimizers are re-created at every epoch (trainer.py:226), so their moments and step counts
 start from zero each epoch; lr_rate *= 0.98 for epochs above 50.
 """
@@ -26,7 +28,7 @@ import torch
 from miscc.config import cfg
 from miscc.utils import mkdir_p, weights_init
 from miscc.shape_losses import ins_discriminator_loss, glb_discriminator_loss, generator_loss, check_pcp_lambda
-from model import SHP_G_NET, INS_D_NET, GLB_D_NET
+from model import SHP_G_NET, INS_D_NET, GLB_D_NET, vgg19_bn, vgg_weights_path
 from trainer import ParamArena, ArenaAdam
 from objgan_hip import ops
 import shapeDataset
@@ -79,10 +81,11 @@ def path_leaf(path):
 
 class condGANTrainer(object):
     def __init__(self, output_dir, data_loader, dataset, device=None):
-        check_pcp_lambda(cfg.TRAIN.SMOOTH.get("PCP_LAMBDA", 0.0))
         self.model_dir = os.path.join(output_dir, 'Model')
+        self.score_dir = os.path.join(output_dir, 'Score')
         if cfg.TRAIN.FLAG:
             mkdir_p(self.model_dir)
+            mkdir_p(self.score_dir)
         self.device = torch.device(device if device is not None else ("cuda:0" if cfg.CUDA else "cpu"))
         self.batch_size = cfg.TRAIN.BATCH_SIZE
         self.max_epoch = cfg.TRAIN.MAX_EPOCH
@@ -95,6 +98,7 @@ class condGANTrainer(object):
         self.num_batches = len(data_loader) if data_loader is not None else 0
         self.clip_norm = float(cfg.TRAIN.get("RNN_GRAD_CLIP", 0.25))
         self.netG = None
+        self.vgg = None
 
     # ---- networks ----
     def build_models(self):
@@ -111,11 +115,19 @@ class condGANTrainer(object):
             for net, leaf in ((netINSD, 'netINSD.pth'), (netGLBD, 'netGLBD.pth')):
                 print('Load %s from: ' % leaf[3:-4], os.path.join(folder, leaf))
                 net.load_state_dict(torch.load(os.path.join(folder, leaf), map_location="cpu"))
-        self.attach(netG, netINSD, netGLBD)
+        vgg = None
+        if float(cfg.TRAIN.SMOOTH.get("PCP_LAMBDA", 0.0)) != 0.0:
+            check_pcp_lambda(cfg.TRAIN.SMOOTH.PCP_LAMBDA, vgg_weights_path())
+            vgg = vgg19_bn(pretrained=True)
+            print('Load the perceptual network from: ', vgg_weights_path())
+        self.attach(netG, netINSD, netGLBD, vgg)
         return [netG, netINSD, netGLBD, epoch]
 
-    def attach(self, netG, netINSD, netGLBD):
-        """move the networks to the device and re-home their parameters into flat arenas"""
+    def attach(self, netG, netINSD, netGLBD, vgg=None):
+        """move the networks to the device and re-home their parameters into flat arenas; vgg: the frozen perceptual
+        network (model.VGG), needed exactly when PCP_LAMBDA != 0"""
+        self.vgg = vgg.to(self.device) if vgg is not None else None
+        self.pcp_score = torch.zeros((), dtype=torch.float32, device=self.device)
         self.netG, self.netINSD, self.netGLBD = (n.to(self.device).train() for n in (netG, netINSD, netGLBD))
         self.arenaG, self.arenaINSD, self.arenaGLBD = (ParamArena(n) for n in (self.netG, self.netINSD, self.netGLBD))
         self.avg_param_G = self.arenaG.flat.clone()
@@ -129,7 +141,8 @@ class condGANTrainer(object):
 
     # ---- one iteration (reference trainer.py:236-285) ----
     def train_step(self, batch, noise=None):
-        """batch: shapeDataset.prepare_data's dict -> the losses and the generator's gradient norm as device scalars"""
+        """batch: shapeDataset.prepare_data's dict -> the losses and the generator's gradient norm as device scalars
+        (gpcp_loss and this step's pcp_score are zeros when the perceptual term is off)"""
         R = batch["max_num_roi"]
         fwd = batch["bbox_maps_fwd"]
         if noise is None:
@@ -155,17 +168,23 @@ class condGANTrainer(object):
         self.arenaGLBD.set_requires_grad(False)
         try:
             with ops.direct_wgrad_scope():
-                errG, (insg, glbg) = generator_loss(self.netINSD, self.netGLBD, None, batch["hmaps"], fake_hmaps, fwd,
-                                                    pooled_maps)
+                res = generator_loss(self.netINSD, self.netGLBD, self.vgg, batch["hmaps"], fake_hmaps, fwd, pooled_maps)
+                errG, logs = res[0], res[1]
+                insg, glbg = logs[0], logs[1]
                 errG.backward()
         finally:
             self.arenaINSD.set_requires_grad(True)
             self.arenaGLBD.set_requires_grad(True)
         self.optimizerG.step()
         ops.ema_update_(self.avg_param_G, self.arenaG.flat, EMA_DECAY)
+        if self.vgg is not None:
+            gpcp, score = logs[2].detach(), res[2]
+            self.pcp_score += score                      # on the device: read once per epoch
+        else:
+            gpcp = score = torch.zeros_like(self.pcp_score)
         return {"errINSD": errINSD.detach(), "errGLBD": errGLBD.detach(), "errG": errG.detach(),
-                "insg_loss": insg.detach(), "glbg_loss": glbg.detach(), "fake_hmaps": fake_hmaps.detach(),
-                "clip": self.optimizerG.clip}
+                "insg_loss": insg.detach(), "glbg_loss": glbg.detach(), "gpcp_loss": gpcp, "pcp_score": score,
+                "fake_hmaps": fake_hmaps.detach(), "clip": self.optimizerG.clip}
 
     # ---- checkpoints ----
     def save_model(self, epoch):
@@ -182,10 +201,22 @@ class condGANTrainer(object):
             torch.save({k: v.detach().cpu().clone() for k, v in net.state_dict().items()},
                        '%s/%s' % (self.model_dir, leaf))
 
+    def write_score(self, epoch):
+        """the epoch's one host read of the accumulated perceptual score (reference trainer.py:304-308; never reset)"""
+        pcp_score = float(self.pcp_score)
+        print('pcp_score: ', pcp_score)
+        with open('%s/scores_%d.txt' % (self.score_dir, epoch), 'w') as f:
+            f.write('pcp_score %f' % pcp_score)
+        return pcp_score
+
     # ---- the loop ----
     def train(self):
         start_epoch = self.build_models()[3]
-        print('Not built here: the perceptual loss term (Score/scores_N.txt) and the DISPLAY_INTERVAL image grids.')
+        if self.vgg is None:
+            print('Not built here: the DISPLAY_INTERVAL image grids.  PCP_LAMBDA = 0: this run leaves the perceptual term '
+                  'out (gpcp_loss and pcp_score stay 0).')
+        else:
+            print('Not built here: the DISPLAY_INTERVAL image grids.')
         gen_iterations = 0
         lr_rate = 1
         for epoch in range(start_epoch, self.max_epoch):
@@ -197,13 +228,16 @@ class condGANTrainer(object):
                 out = self.train_step(shapeDataset.prepare_data(data, self.device, self.num_classes))
                 gen_iterations += 1
                 if gen_iterations % self.print_interval == 0:
-                    vals = {k: float(out[k]) for k in ("errINSD", "errGLBD", "insg_loss", "glbg_loss")}
+                    vals = {k: float(out[k]) for k in ("errINSD", "errGLBD", "insg_loss", "glbg_loss", "gpcp_loss")}
                     elapsed = time.time() - start_t
                     print('| epoch {:3d} | {:5d}/{:5d} batches | ms/batch {:5.2f} | '
                           .format(epoch, step, self.num_batches, elapsed * 1000. / self.print_interval))
-                    print('errINSD: %.2f \nerrGLBD: %.2f \ninsg_loss: %.2f glbg_loss: %.2f '
-                          % (vals["errINSD"], vals["errGLBD"], vals["insg_loss"], vals["glbg_loss"]))
+                    # (the reference's G_logs; without the term -- PCP_LAMBDA = 0 -- the line keeps its two entries)
+                    pcp = 'gpcp_loss: %.2f ' % vals["gpcp_loss"] if self.vgg is not None else ''
+                    print('errINSD: %.2f \nerrGLBD: %.2f \ninsg_loss: %.2f glbg_loss: %.2f %s'
+                          % (vals["errINSD"], vals["errGLBD"], vals["insg_loss"], vals["glbg_loss"], pcp))
                     start_t = time.time()
+            self.write_score(epoch)
             if epoch % self.snapshot_interval == 0:
                 self.save_model(epoch)
         self.save_model(self.max_epoch)

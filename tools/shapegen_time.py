@@ -9,7 +9,19 @@
 Device events around `--steps` passes after `--warmup` passes.  Prints one JSON line; `--out` also writes it to a file.
 `--step-only`: just the step loop (the run to put under a kernel trace).  Not a test: asserts nothing about time.
 
+`--pcp`: the cost of the perceptual term instead, at the reference batch of 40 and at 16 in ONE call.  The frozen
+VGG-19-bn comes from `--vgg-weights FILE` (torchvision's vgg19_bn-c79401a0.pth) or, without a file, from seeded
+full-width weights.  Per batch size, alternating runs on the same seeded batch:
+  * the whole training step with PCP_LAMBDA = 10 against the same tree with PCP_LAMBDA = 0.  The difference is the COST
+    OF THE TERM (about 3 B VGG-19 passes: 2 B forward, B data gradient), not a regression of anything;
+  * the term alone (`VGG.perceptual` forward + backward);
+  * the new memory-bound kernels (stem pair, l1_tap_forward, l1_tap_backward) replayed at every tap's shape: their
+    time over the bytes they must move, as a share of the HBM peak (8 TB/s);
+  * the convolutions inside the term: algorithmic FLOP (forward on 2 B images, data gradient on B, Linears included)
+    over the term's time minus the replayed kernels' time (the five pool passes stay in that remainder).
+
     python tools/shapegen_time.py [--B 40] [--R 10] [--nbf 80] [--steps 10] [--warmup 3] [--out FILE] [--step-only]
+    python tools/shapegen_time.py --pcp [--vgg-weights FILE] [--pcp-batches 40,16] [--steps 5] [--warmup 2] [--out FILE]
 """
 import argparse
 import json
@@ -55,6 +67,133 @@ def timed(fn, steps, warmup):
     return t0.elapsed_time(t1) / steps
 
 
+HBM_PEAK = 8.0e12          # bytes / s, MI355X
+
+
+def seeded_vgg_state(seed=331):
+    """full-width weights in torchvision's layout: N(0, 2 / fan_in) banks, running variances 0.5 + U(0, 1)"""
+    import model
+    g = torch.Generator().manual_seed(seed)
+    sd = model.vgg_init_state()
+    for k in sorted(sd):
+        t = sd[k]
+        if t.dim() > 1:
+            t.copy_(torch.randn(t.shape, generator=g) * (2.0 / t[0].numel()) ** 0.5)
+        elif k.endswith("running_var"):
+            t.copy_(0.5 + torch.rand(t.shape, generator=g))
+        elif k.endswith("running_mean"):
+            t.copy_(0.1 * torch.randn(t.shape, generator=g))
+    return sd
+
+
+def pcp_glue(vgg, B, dev, steps, warmup):
+    """replay of the new kernels at the term's shapes -> (ms, bytes) per kernel family for ONE training step"""
+    from objgan_hip import ops
+    shapes, x = [], (2 * B, 3, 224, 224)
+    for layer in vgg.layers():
+        if layer[0] == "pool":
+            x = (x[0], x[1], x[2] // 2, x[3] // 2)
+            continue
+        x = (x[0], layer[1].shape[0], x[2], x[3]) if layer[0] == "conv" else (x[0], layer[1].shape[0], 1, 1)
+        shapes.append((layer[0] == "conv" or layer[3], B * x[1] * x[2] * x[3]))
+    out = {}
+    xs = torch.rand(2 * B, 1, 64, 64, device=dev)
+    dy = torch.randn(B, 3, 224, 224, device=dev)
+    out["stem_forward"] = (timed(lambda: ops.pcp_stem_forward(xs), steps, warmup), 4.0 * (xs.numel() + 2 * B * 3 * 224 * 224))
+    out["stem_backward"] = (timed(lambda: ops.pcp_stem_backward(dy, 64), steps, warmup), 4.0 * (dy.numel() + B * 64 * 64))
+    means = torch.empty(len(shapes), device=dev)
+    coef = torch.full((1,), 1e-6, device=dev)
+    fwd_ms = bwd_ms = fwd_b = bwd_b = 0.0
+    for slot, (relu, n) in enumerate(shapes):
+        f, r, gd = (torch.relu(torch.randn(n, device=dev)) for _ in range(3))
+        last = slot == len(shapes) - 1
+        fwd_ms += timed(lambda: ops.l1_tap_forward(f, r, means, slot), steps, warmup)
+        bwd_ms += timed(lambda: ops.l1_tap_backward(f, r, None if last else gd, coef, relu), steps, warmup)
+        fwd_b += 8.0 * n
+        bwd_b += (12.0 if last else 16.0) * n
+        del f, r, gd
+    out["l1_tap_forward"] = (fwd_ms, fwd_b)
+    out["l1_tap_backward"] = (bwd_ms, bwd_b)
+    return out
+
+
+def pcp_conv_flop(vgg, B):
+    flop, x = 0.0, (3, 224, 224)
+    for layer in vgg.layers():
+        if layer[0] == "pool":
+            x = (x[0], x[1] // 2, x[2] // 2)
+            continue
+        w = layer[1]
+        px = x[1] * x[2] if layer[0] == "conv" else 1
+        flop += 2.0 * w.numel() * px * 3 * B           # forward on 2 B images + data gradient on B
+        x = (w.shape[0], x[1], x[2]) if layer[0] == "conv" else (w.shape[0], 1, 1)
+    return flop
+
+
+def pcp_main(a, dev):
+    """--pcp: see the module docstring"""
+    import tempfile
+    import model
+    import shape_trainer
+    from miscc.config import cfg
+    from objgan_hip import ops
+    sd = torch.load(a.vgg_weights, map_location="cpu") if a.vgg_weights else seeded_vgg_state()
+    res = {"mode": "pcp", "R": a.R, "nbf": a.nbf, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds,
+           "conv_math": ops.get_conv_math(), "weights": a.vgg_weights or "seeded full-width", "hbm_peak_bytes_per_s": HBM_PEAK,
+           "note": "term_cost_ms is the cost of the perceptual term (about 3 B VGG-19 passes), not a regression", "batches": {}}
+    ds = type("DS", (), {"cats_dict": {}, "cats_index_dict": {i: i for i in range(a.nbf)}})()
+    vgg = model.VGG(sd).to(dev)
+    del sd
+    for B in [int(v) for v in a.pcp_batches.split(",")]:
+        cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.FLAG, cfg.GAN.R_NUM = B, True, 1
+        cfg.TRAIN.SMOOTH.INS_LAMBDA, cfg.TRAIN.SMOOTH.GLB_LAMBDA = 1.0, 1.0
+        batch = inputs(B, a.R, a.nbf, dev)
+        trainers = {}
+        for lam in (0.0, 10.0):
+            torch.manual_seed(0)
+            cfg.TRAIN.SMOOTH.PCP_LAMBDA = 0.0               # (build_models would look for the weights file)
+            t = shape_trainer.condGANTrainer(tempfile.mkdtemp(prefix="shapegen_time_"), None, ds, device=dev)
+            t.build_models()
+            if lam:
+                t.vgg = vgg
+            t.define_optimizers(1.0)
+            trainers[lam] = t
+
+        def step(lam):
+            cfg.TRAIN.SMOOTH.PCP_LAMBDA = lam
+            return trainers[lam].train_step(batch)
+
+        fp = batch["pooled_hmaps"].clone().requires_grad_()
+        rp = torch.rand_like(fp)
+
+        def term():
+            fp.grad = None
+            (vgg.perceptual(fp, rp).sum() * 10.0).backward()
+
+        ms = {"lambda_0": [], "lambda_10": [], "term_alone": []}
+        for _ in range(a.rounds):                            # alternate
+            ms["lambda_0"].append(timed(lambda: step(0.0), a.steps, a.warmup))
+            ms["lambda_10"].append(timed(lambda: step(10.0), a.steps, a.warmup))
+            ms["term_alone"].append(timed(term, a.steps, a.warmup))
+        glue = pcp_glue(vgg, B, dev, a.steps, a.warmup)
+        glue_ms = sum(v[0] for v in glue.values())
+        term_ms = min(ms["term_alone"])
+        flop = pcp_conv_flop(vgg, B)
+        res["batches"][str(B)] = {
+            "step_ms": ms, "term_cost_ms": min(ms["lambda_10"]) - min(ms["lambda_0"]),
+            "new_kernels": {k: {"ms": v[0], "bytes": v[1], "share_of_hbm_peak": v[1] / (v[0] * 1e-3) / HBM_PEAK}
+                            for k, v in glue.items()},
+            "new_kernels_total": {"ms": glue_ms, "bytes": sum(v[1] for v in glue.values()),
+                                  "share_of_hbm_peak": sum(v[1] for v in glue.values()) / (glue_ms * 1e-3) / HBM_PEAK},
+            "convolutions": {"algorithmic_tflop": flop / 1e12, "ms": term_ms - glue_ms,
+                             "tflops": flop / ((term_ms - glue_ms) * 1e-3) / 1e12,
+                             "what": "term alone minus the replayed new kernels; the five pool passes stay in the remainder"}}
+        cfg.TRAIN.SMOOTH.PCP_LAMBDA = 0.0
+        del trainers, batch
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=40)
@@ -65,9 +204,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", type=str, default="")
     ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--pcp", action="store_true")
+    ap.add_argument("--vgg-weights", type=str, default="")
+    ap.add_argument("--pcp-batches", type=str, default="40,16")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = torch.device("cuda:0")
+    if a.pcp:
+        line = json.dumps(pcp_main(a, dev))
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     from miscc.config import cfg
     from objgan_hip import ops, _lib
     import shape_trainer
