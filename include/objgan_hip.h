@@ -519,6 +519,25 @@ int objgan_box_max_backward(const float* dy, const unsigned char* arg, float* dx
 int objgan_boxmaps_onehot(const float* raw, const int* cat, const int* num, float* fwd, float* bwd, int B, int NB, int R,
                           int C, int SS, void* stream);
 
+/* ---- layout stage (csrc/layout.hip): decoder samples -> box tables and box maps, the file route of
+ * seq2seq/evaluator (postprocess, write_layouts) and miscc/load.py (load_gen_insanns, get_gen_rois) without the files.
+ * labels [B][T], lengths [B], samples [B][T][4]: the outputs of objgan_box_decode.  mean_std [8] doubles: (mean, std) of
+ * x, y, w, r.  label_to_cat [L]: decoder label -> category id (-1: none); cat_to_rel [ncat]: category id -> row of
+ * categories.txt (-1: unknown); thresholds [B][L]: count caps per caption and label.  All of these in device memory.
+ * boxes [B][T][5] doubles (x, y, w, h, category id; zero past nbox[b]) and nbox [B]: bit for bit Evaluator.postprocess.
+ * rois [NB][B][R][6], fm_rois [B][R][6] doubles, num_rois [B], cats [B][R] (relative category; 0 in unused slots),
+ * maps [B][R][S][S] and fmaps [B][R][F][F] floats (1 inside a box's rectangle): what load_gen_insanns builds from the
+ * '%.2f' rows of those boxes.  sizes: HOST array of the NB <= 4 branch sides, S = sizes[0]; min_size: boxes with both
+ * sides below it are dropped; R <= 64.  bounds: scratch, 8 B R ints.  Two launches, no atomics, no host read.
+ * tie_rule: the order np.argsort gives EQUAL areas when more than R boxes are left -- 0: insertion sort (numpy's generic
+ * code up to 16 values; after the reversal the later box comes first), 1: numpy's AVX-512 network for 64-bit keys; other
+ * values return 0.  T > 17 returns 0: past 16 boxes neither rule describes numpy's argsort. */
+int objgan_layout_from_decode(const int* labels, const int* lengths, const double* samples, const double* mean_std,
+                              const int* label_to_cat, const int* cat_to_rel, const int* thresholds,
+                              double* boxes, int* nbox, double* rois, double* fm_rois, int* num_rois, int* cats,
+                              float* maps, float* fmaps, int* bounds, const int* sizes, int NB, int F, int R,
+                              int min_size, int tie_rule, int B, int T, int L, int ncat, void* stream);
+
 /* ---- perceptual term of the shape generator's loss (csrc/perceptual.hip) -------------------------
  * pcp_stem_forward: y[N][3][OH][OW] = (bilinear_align_corners(x[N][1][S][S]) - mean_c) / std_c with the ImageNet
  *     constants mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225); S == 1 and OH / OW == 1 are scale 0.

@@ -102,6 +102,7 @@ SIGNATURES = {
     "objgan_box_max_forward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
     "objgan_box_max_backward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],
     "objgan_boxmaps_onehot": [_ptr] * 5 + [_c_int] * 5 + [_ptr],
+    "objgan_layout_from_decode": [_ptr] * 17 + [_c_int] * 9 + [_ptr],
     "objgan_pcp_stem_forward": [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr],
     "objgan_pcp_stem_backward": [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr],
     "objgan_l1_tap_forward": [_ptr, _ptr, _c_long, _ptr, _c_int, _ptr, _ptr],

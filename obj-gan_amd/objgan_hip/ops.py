@@ -2567,6 +2567,87 @@ def boxmaps_onehot(raw, cats, num_rois, R, C):
 
 
 # ----------------------------------------------------------------------------------------------
+# layout stage: decoder samples -> box tables and box maps (csrc/layout.hip)
+# ----------------------------------------------------------------------------------------------
+LAYOUT_MAX_T = 17       # <= 16 boxes reach the area ranking: numpy sorts that many by insertion, ties are defined
+
+
+_ARGSORT_PROBES = (      # (keys, np.argsort of them through numpy's AVX-512 network for 64-bit keys)
+    ((3, 1, 2, 1, 3, 3, 1, 2, 2, 1, 3, 1, 2, 3, 1, 2), (1, 3, 6, 9, 11, 14, 7, 2, 15, 12, 8, 0, 4, 5, 10, 13)),
+    ((2, 2, 1, 1, 2, 1, 2, 2, 1, 1, 2, 1), (3, 2, 5, 8, 9, 11, 0, 1, 7, 6, 4, 10)),
+    ((1, 0, 1, 0, 1, 1, 0, 0), (1, 3, 6, 7, 2, 0, 5, 4)))
+_TIE_RULE = []
+
+
+def argsort_tie_rule():
+    """How this host's np.argsort orders EQUAL float64 keys among up to 16 values: 0 -- as a stable sort (numpy's generic
+    code sorts that many by insertion), 1 -- as numpy's AVX-512 sorting network; None when it is neither.  The file
+    route picks the BOXES_NUM largest boxes with np.argsort; `layout_from_decode` follows the same rule (probed once)."""
+    if not _TIE_RULE:
+        import numpy as np
+        got = [np.argsort(np.array(k, dtype=np.float64)).tolist() for k, _ in _ARGSORT_PROBES]
+        stable = [np.argsort(np.array(k, dtype=np.float64), kind="stable").tolist() for k, _ in _ARGSORT_PROBES]
+        _TIE_RULE.append(0 if got == stable else 1 if got == [list(w) for _, w in _ARGSORT_PROBES] else None)
+    return _TIE_RULE[0]
+
+
+def layout_from_decode(labels, lengths, samples, mean_std, label_to_cat, cat_to_rel, thresholds, imsize, fmsize, R,
+                       min_size=10, tie_rule=None):
+    """The outputs of `box_decode` -> what the file route (Evaluator.postprocess, write_layouts, load_gen_insanns,
+    get_gen_rois) builds from them, without a file and without a host read.
+    labels [B, T] int32, lengths [B] int32, samples [B, T, 4] float64; mean_std [8] float64 (mean, std of x, y, w, r);
+    label_to_cat [L] int32 (decoder label -> category id, -1: none); cat_to_rel [maxcat + 1] int32 (category id -> row of
+    categories.txt, -1: unknown); thresholds [B, L] int32 count caps; imsize: the branch sides; min_size:
+    cfg.ROI.ROI_MIN_SIZE; tie_rule: the order of equal areas when more than R boxes are left (default: what np.argsort
+    does on this host, `argsort_tie_rule`; refused when that is unknown and T - 1 > R).  Returns a dict: boxes [B, T, 5] float64 and nbox [B] int32 (postprocess); rois (list per
+    branch of [B, R, 6] float64), fm_rois [B, R, 6], num_rois [B] int32, cats [B, R] int32, raw_maps [B, R, S, S] and
+    raw_fmaps [B, R, fmsize, fmsize] float32."""
+    i32, f64 = torch.int32, torch.float64
+    ints = (labels, lengths, label_to_cat, cat_to_rel, thresholds)
+    if any(not t.is_cuda for t in ints + (samples, mean_std)):
+        raise _lib.ObjganHipError("layout_from_decode: every tensor lives on the GPU; there is no CPU path")
+    if any(t.dtype != i32 for t in ints) or samples.dtype != f64 or mean_std.dtype != f64:
+        raise _lib.ObjganHipError("layout_from_decode: labels, lengths, label_to_cat, cat_to_rel and thresholds are int32, "
+                                  "samples and mean_std float64")
+    if labels.dim() != 2:
+        raise _lib.ObjganHipError("layout_from_decode: labels must be [B, T]")
+    B, T = labels.shape
+    L = label_to_cat.numel()
+    imsize = [int(s) for s in imsize]
+    NB, S, F, R = len(imsize), imsize[0], int(fmsize), int(R)
+    if (tuple(lengths.shape) != (B,) or tuple(samples.shape) != (B, T, 4) or mean_std.numel() != 8
+            or tuple(thresholds.shape) != (B, L) or cat_to_rel.numel() < 1):
+        raise _lib.ObjganHipError("layout_from_decode: inconsistent shapes")
+    if T > LAYOUT_MAX_T:
+        raise _lib.ObjganHipError("layout_from_decode: T = %d decode steps; past %d the order in which the file route "
+                                  "keeps boxes of equal area is not defined" % (T, LAYOUT_MAX_T))
+    if tie_rule is None:
+        tie_rule = argsort_tie_rule()
+        if tie_rule is None:
+            if T - 1 > R:
+                raise _lib.ObjganHipError("layout_from_decode: np.argsort on this host orders equal keys in a way this "
+                                          "kernel does not know, and %d decode steps can leave more than %d boxes: pass "
+                                          "tie_rule" % (T, R))
+            tie_rule = 0                        # at most R boxes: no cut, the rule is never used
+    dev = labels.device
+    boxes = torch.empty((B, T, 5), dtype=f64, device=dev)
+    nbox = torch.empty((B,), dtype=i32, device=dev)
+    rois = torch.empty((NB, B, R, 6), dtype=f64, device=dev)
+    fm_rois = torch.empty((B, R, 6), dtype=f64, device=dev)
+    num_rois = torch.empty((B,), dtype=i32, device=dev)
+    cats = torch.empty((B, R), dtype=i32, device=dev)
+    maps = torch.empty((B, R, S, S), dtype=_F32, device=dev)
+    fmaps = torch.empty((B, R, F, F), dtype=_F32, device=dev)
+    bounds = torch.empty((B, R, 8), dtype=i32, device=dev)
+    _lib.call("objgan_layout_from_decode", _p(_c(labels)), _p(_c(lengths)), _p(_c(samples)), _p(_c(mean_std)),
+              _p(_c(label_to_cat)), _p(_c(cat_to_rel)), _p(_c(thresholds)), _p(boxes), _p(nbox), _p(rois), _p(fm_rois),
+              _p(num_rois), _p(cats), _p(maps), _p(fmaps), _p(bounds), _iarr(imsize), NB, F, R, int(min_size), int(tie_rule), B, T, L,
+              cat_to_rel.numel(), _stream())
+    return {"boxes": boxes, "nbox": nbox, "rois": [rois[i] for i in range(NB)], "fm_rois": fm_rois,
+            "num_rois": num_rois, "cats": cats, "raw_maps": maps, "raw_fmaps": fmaps}
+
+
+# ----------------------------------------------------------------------------------------------
 # perceptual term of the shape generator's loss (csrc/perceptual.hip)
 # ----------------------------------------------------------------------------------------------
 PCP_SIZE = 224          # the frozen network's input side (reference shape_generation/model.py:301)

@@ -103,6 +103,47 @@ class Evaluator(object):
             fout_all.close()
         return layouts
 
+    # ---- the tables of the device layout stage (objgan_hip.ops.layout_from_decode) ---------------------------------
+    UNCAPPED = 1 << 30          # count cap of a label that names no category (<pad>, <sos>, <eos>, <unk>): never reached
+
+    def label_categories(self):
+        """[L] int64: decoder label index -> category id, int(index2word[l]); -1 where the word is not a number"""
+        L = len(self.dev_label_lang.index2word)
+        out = np.full((L,), -1, np.int64)
+        for l in range(L):
+            word = str(self.dev_label_lang.index2word[l])
+            if word.isdigit():
+                out[l] = int(word)
+        return out
+
+    def layout_tables(self, cats_index_dict, device=None):
+        """-> (mean_std [8] float64: mean and std of x, y, w, r; label_to_cat [L] int32; cat_to_rel [maxcat + 1] int32:
+        `cats_index_dict` as a table, -1 for an id it does not hold), on `device`: the constant inputs of
+        ops.layout_from_decode, which restates `postprocess` and the readers of the files `write_layouts` writes."""
+        mean_std = torch.tensor([float(v) for pair in (self.x_mean_std, self.y_mean_std, self.w_mean_std,
+                                                       self.r_mean_std) for v in pair[:2]], dtype=torch.float64)
+        label_to_cat = torch.from_numpy(self.label_categories().astype(np.int32))
+        cat_to_rel = np.full((max(int(c) for c in cats_index_dict) + 1,), -1, np.int32)
+        for cat, rel in cats_index_dict.items():
+            cat_to_rel[int(cat)] = int(rel)
+        tables = (mean_std, label_to_cat, torch.from_numpy(cat_to_rel))
+        return tables if device is None else tuple(t.to(device) for t in tables)
+
+    def draw_thresholds(self, rng, B):
+        """[B, L] int32 count caps, max(int(normal(mu_l, sigma_l)), 2) for every (caption, label) in ONE draw; labels
+        that name no category (or one `gaussian_dict` does not hold) get UNCAPPED.  The law of `postprocess`'s
+        per-category draws, from another stream: `postprocess` draws only for the categories a caption shows, in order
+        of appearance, so a seeded run reproduces the distribution of the file route's layouts, not its samples."""
+        rng = np.random if rng is None else rng
+        cats = self.label_categories()
+        known = np.array([c >= 0 and int(c) in self.gaussian_dict for c in cats], bool)
+        mu = np.array([self.gaussian_dict[int(c)][0] if k else 0.0 for c, k in zip(cats, known)], np.float64)
+        sigma = np.array([self.gaussian_dict[int(c)][1] if k else 0.0 for c, k in zip(cats, known)], np.float64)
+        draw = np.trunc(rng.normal(mu, sigma, size=(int(B), len(cats))))           # int(): toward zero
+        caps = np.maximum(np.clip(draw, -self.UNCAPPED, self.UNCAPPED).astype(np.int64), 2)
+        caps[:, ~known] = self.UNCAPPED
+        return caps.astype(np.int32)
+
     # ---- the device part ----------------------------------------------------------------------------------------
     def decode(self, encoder, decoder, data, rng=None, noise=None):
         """-> per caption (sequence, xy, wh) and the caption ids; `batch_size` captions per launch.  noise: [N, T, 6]
