@@ -492,13 +492,32 @@ if _PACK_LOG is not None:
 def _pack_log(kind, w, cached):
     """development: which calls still pack their bank themselves (a pack_weights_kernel launch per call)?"""
     import traceback
-    where = " < ".join("%s:%d" % (f.name, f.lineno) for f in traceback.extract_stack(limit=9)[:-2][::-1][:6])
+    where = " < ".join("%s:%d" % (f.name, f.lineno) for f in traceback.extract_stack(limit=10)[:-3][::-1][:6])
     key = "%s %s cached=%s  %s" % (kind, tuple(w.shape), cached, where)
     _PACK_LOG[key] = _PACK_LOG.get(key, 0) + 1
 
 
 def _job_blob():
     return ctypes.create_string_buffer(_q("objgan_conv_pack_job_bytes"))
+
+
+def _bank_acquire(key, w, nfloats, device, make_jobs, kind):
+    """-> (wt, packed): the buffer of the packed image of w for one launch and whether its contents are current (the
+    library packs it inside the call otherwise).  key: `_pack_key(...)` -- the bank is the cached one, re-packed IN PLACE
+    when stale; `make_jobs(wt)` builds its pack-job blobs on first use (what repack_arena() runs from its device
+    table) -- or None (temporaries, weights nobody vouches for): pack per call, keep nothing.  kind: the pack log's
+    name of the call site."""
+    if key is not None:
+        ent, fresh = _bank_lookup(key, w, nfloats, device)
+        wt, packed = ent.wt, int(fresh)
+        if ent.jobs is None:
+            ent.jobs = make_jobs(wt)
+        _bank_mark(ent)
+    else:
+        wt, packed = torch.empty(nfloats, dtype=_F32, device=device), 0
+    if _PACK_LOG is not None and not packed:
+        _pack_log(kind, w, key is not None)
+    return wt, packed
 
 
 # bf16 mode (BASELINE config 5): the matrix kernels read their pixel operand from a bf16 channel-blocked copy [N][C/16][H][W][16] of the source
@@ -539,21 +558,15 @@ def _igemm(x, w, bias, y, N, C, H, W, upsample, pad_mode, Cout, Cin, Torig, tran
         rec = _records(x, xmax, N, C, H * W, 2.0 * M * Tg * PH * PW / float(H * W), M)
         if rec is not None:
             kmath, xk = 5, rec
+
+    def pack_jobs(wt):
+        job = _job_blob()
+        _lib.call("objgan_conv_pack_job", job, _p(w), _p(wt), N, C, H, W, Cout, Cin, Torig, int(transpose),
+                  Tg, _iarr(src_tap), PH, PW, act, math)
+        return [job.raw]
+
     key = _pack_key(w, transpose, src_tap, layout, math) if cache else None      # (temporaries: pack per call, keep nothing)
-    nfl = _q("objgan_conv_packed_floats", int(M), int(C), int(Tg))
-    if key is not None:
-        ent, fresh = _bank_lookup(key, w, nfl, x.device)
-        wt, packed = ent.wt, int(fresh)
-        if ent.jobs is None:
-            job = _job_blob()
-            _lib.call("objgan_conv_pack_job", job, _p(w), _p(wt), N, C, H, W, Cout, Cin, Torig, int(transpose),
-                      Tg, _iarr(src_tap), PH, PW, act, math)
-            ent.jobs = [job.raw]
-        _bank_mark(ent)
-    else:
-        wt, packed = torch.empty(nfl, dtype=_F32, device=x.device), 0
-    if _PACK_LOG is not None and not packed:
-        _pack_log("igemm", w, key is not None)
+    wt, packed = _bank_acquire(key, w, _q("objgan_conv_packed_floats", int(M), int(C), int(Tg)), x.device, pack_jobs, "igemm")
     # split-K launches (small grids, long reductions) go through a workspace: partial tiles, then an ordered sum
     nws = _q("objgan_conv_igemm_ws_floats", N, C, H, W, int(upsample), int(pad_mode), Cout, Cin, Torig,
                                                    int(transpose), Tg, PH, PW, stride, OHf, OWf, osh, osw, act,
@@ -578,12 +591,9 @@ def _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, k, pad_h, pad_w, LH, LW, cachea
         return None
     dh, dw, st = [], [], []
     for a in range(2):
-        khs = [kh for kh in range(KH) if (a + pad_h - kh) % 2 == 0]
         for b in range(2):
-            kws = [kw for kw in range(KW) if (b + pad_w - kw) % 2 == 0]
-            dh += [(a + pad_h - kh) // 2 for kh in khs for kw in kws]
-            dw += [(b + pad_w - kw) // 2 for kh in khs for kw in kws]
-            st += [kh * KW + kw for kh in khs for kw in kws]
+            th, tw, ts = _taps(KH, KW, a + pad_h, b + pad_w, 2)
+            dh, dw, st = dh + th, dw + tw, st + ts
     Tg = len(st) // 4
     if Tg > 8:
         return None
@@ -596,22 +606,17 @@ def _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, k, pad_h, pad_w, LH, LW, cachea
     xmax = _absmax(g) if math == 4 else None
     if math == 4 and _H2_CENSUS is not None:
         _census("data gradient: filter columns (input channels)", w, 1, site)
-    key = _pack_key(w, 2, st, False, math) if cacheable else None
-    if key is not None:
-        ent, fresh = _bank_lookup(key, w, n, g.device)
-        wt, packed = ent.wt, int(fresh)
-        if ent.jobs is None:
-            ent.jobs = []
-            for ph in range(4):
-                job = _job_blob()
-                _lib.call("objgan_conv_pack_job_phase", job, _p(w), _p(wt), Cout, Cin, KH * KW, Tg,
-                          _iarr(st[ph * Tg:(ph + 1) * Tg]), ph, math)
-                ent.jobs.append(job.raw)
-        _bank_mark(ent)
-    else:
-        wt, packed = torch.empty(n, dtype=_F32, device=g.device), 0
-    if _PACK_LOG is not None and not packed:
-        _pack_log("phases", w, key is not None)
+
+    def pack_jobs(wt):
+        jobs = []
+        for ph in range(4):
+            job = _job_blob()
+            _lib.call("objgan_conv_pack_job_phase", job, _p(w), _p(wt), Cout, Cin, KH * KW, Tg,
+                      _iarr(st[ph * Tg:(ph + 1) * Tg]), ph, math)
+            jobs.append(job.raw)
+        return jobs
+
+    wt, packed = _bank_acquire(_pack_key(w, 2, st, False, math) if cacheable else None, w, n, g.device, pack_jobs, "phases")
     nws = _q("objgan_conv_dgrad_s2_phases_ws_floats", N, Cout, OH, OW, math)
     ws = torch.empty(nws, dtype=_F32, device=g.device) if nws > 0 and _BF16_CHANNELS_LAST else None
     nws = nws if ws is not None else 0
@@ -634,21 +639,16 @@ def _dgrad_s2_thin(g, w, N, Cout, OH, OW, Cin, cacheable=True):
     read twice instead of once per phase."""
     dx = torch.empty((N, Cin, 2 * OH, 2 * OW), dtype=_F32, device=g.device)
     n = _q("objgan_conv_dgrad_s2_thin_floats", Cout, Cin)
-    key = _pack_key(w, 3, (0,), "thin4", 0) if cacheable else None
-    if key is not None:
-        ent, fresh = _bank_lookup(key, w, n, g.device)
-        wt, packed = ent.wt, int(fresh)
-        if ent.jobs is None:
-            ent.jobs = []
-            for ph in range(4):
-                job = _job_blob()
-                _lib.call("objgan_conv_pack_job_thin_phase", job, _p(w), _p(wt), Cout, Cin, ph)
-                ent.jobs.append(job.raw)
-        _bank_mark(ent)
-    else:
-        wt, packed = torch.empty(n, dtype=_F32, device=g.device), 0
-    if _PACK_LOG is not None and not packed:
-        _pack_log("thin4", w, key is not None)
+
+    def pack_jobs(wt):
+        jobs = []
+        for ph in range(4):
+            job = _job_blob()
+            _lib.call("objgan_conv_pack_job_thin_phase", job, _p(w), _p(wt), Cout, Cin, ph)
+            jobs.append(job.raw)
+        return jobs
+
+    wt, packed = _bank_acquire(_pack_key(w, 3, (0,), "thin4", 0) if cacheable else None, w, n, g.device, pack_jobs, "thin4")
     _lib.call("objgan_conv_dgrad_s2_thin", _p(g), _p(w), _p(dx), _p(wt), N, Cout, OH, OW, Cin, packed, _stream())
     return dx
 
@@ -657,20 +657,39 @@ def conv_out_size(L, k, s, p):
     return (L + 2 * p - k) // s + 1
 
 
+def _pair(v):
+    return (v, v) if isinstance(v, int) else v
+
+
+def _taps(KH, KW, oh, ow, step=1, sign=1):
+    """(dh, dw, source tap) lists of one launch, row-major over the filter: the taps (kh, kw) with step | oh - kh and
+    step | ow - kw, each at pixel offset sign * ((oh - kh) / step, (ow - kw) / step).  step 1: every tap -- the forward
+    lists (sign -1, o = padding) and the stride-1 data gradient's; step 2: the taps that reach one output parity phase
+    (a, b) of a stride-2 data gradient, o = (a + pad_h, b + pad_w)."""
+    khs = [kh for kh in range(KH) if (oh - kh) % step == 0]
+    kws = [kw for kw in range(KW) if (ow - kw) % step == 0]
+    return ([sign * ((oh - kh) // step) for kh in khs for kw in kws],
+            [sign * ((ow - kw) // step) for kh in khs for kw in kws],
+            [kh * KW + kw for kh in khs for kw in kws])
+
+
 def _conv_fwd(x, w, bias, stride, pad, refl, upsample, act):
-    """y = act(conv(x, w) + bias); x [N, Cin, H, W] (nearest x2 lifted when `upsample`), w [Cout, Cin, k, k]."""
+    """y = act(conv(x, w) + bias); x [N, Cin, H, W] (nearest x2 lifted when `upsample`), w [Cout, Cin, KH, KW] (the
+    frozen Inception banks are rectangular), pad: an int or (pad_h, pad_w)."""
     N, Cin, H, W = x.shape
-    Cout, k = w.shape[0], w.shape[2]
+    Cout, Cin2, KH, KW = w.shape
+    if Cin2 != Cin or KH * KW > 32:
+        raise _lib.ObjganHipError("convolution: unsupported filter %s for input %s" % (tuple(w.shape), tuple(x.shape)))
+    ph, pw = _pair(pad)
     LH, LW = (2 * H, 2 * W) if upsample else (H, W)
-    OH, OW = conv_out_size(LH, k, stride, pad), conv_out_size(LW, k, stride, pad)
+    OH, OW = conv_out_size(LH, KH, stride, ph), conv_out_size(LW, KW, stride, pw)
     y = torch.empty((N, Cout, OH, OW), dtype=_F32, device=x.device)
-    dh = [kh - pad for kh in range(k) for kw in range(k)]
-    dw = [kw - pad for kh in range(k) for kw in range(k)]
-    st = list(range(k * k))
-    # a convolution with a fused LeakyReLU / ReLU feeds the next convolution directly (discriminator encoders): its
-    # epilogue leaves the partial maxima of y for that consumer's fp16x2 scale
+    dh, dw, st = _taps(KH, KW, ph, pw, sign=-1)
+    # a convolution with a fused LeakyReLU / ReLU feeds the next convolution directly (discriminator encoders, and the
+    # frozen encoder's convolutions through their fused ReLU): its epilogue leaves the partial maxima of y for that
+    # consumer's fp16x2 scale
     ym = _amax_zeroed(x.device) if (act in ("lrelu", "relu") and _amax_wanted(y.numel())) else None
-    _igemm(x, w, bias, y, N, Cin, H, W, upsample, refl, Cout, Cin, k * k, 0,
+    _igemm(x, w, bias, y, N, Cin, H, W, upsample, refl, Cout, Cin, KH * KW, 0,
            dh, dw, st, OH, OW, stride, OH, OW, 1, 1, 0, 0, _ACT[act], ymax=ym)
     if ym is not None:
         _amax_attach(y, ym)
@@ -678,29 +697,30 @@ def _conv_fwd(x, w, bias, stride, pad, refl, upsample, act):
 
 
 def _conv_dgrad(g, w, N, Cin, H, W, stride, pad, refl, upsample, cacheable=True):
-    """Gradient w.r.t. the input [N, Cin, H, W] of conv(x, w) given g = dL/d(conv output)."""
-    Cout, k = w.shape[0], w.shape[2]
+    """Gradient w.r.t. the input [N, Cin, H, W] of conv(x, w) given g = dL/d(conv output); w [Cout, Cin, KH, KW],
+    pad: an int or (pad_h, pad_w)."""
+    Cout, KH, KW = w.shape[0], w.shape[2], w.shape[3]
+    T = KH * KW
+    ph, pw = _pair(pad)
     OH, OW = g.shape[2], g.shape[3]
     LH, LW = (2 * H, 2 * W) if upsample else (H, W)
     if stride == 1:
-        pe = 0 if refl else pad            # reflect: gradient w.r.t. the padded tensor first
-        TH, TW = (LH + 2 * pad, LW + 2 * pad) if refl else (LH, LW)
-        dh = [pe - kh for kh in range(k) for kw in range(k)]
-        dw = [pe - kw for kh in range(k) for kw in range(k)]
-        st = list(range(k * k))
-        ring_ok = (refl and pad == 1 and LH >= 3 and LW >= 3 and
-                   (_q("objgan_conv_bank_layout", N, Cout, OH, OW, Cin, k * k, TH, TW, 0, _MATH["mode"]) & 255) in (1, 3, 4, 5))
+        # reflect: gradient w.r.t. the padded tensor first
+        TH, TW = (LH + 2 * ph, LW + 2 * pw) if refl else (LH, LW)
+        dh, dw, st = _taps(KH, KW, 0, 0) if refl else _taps(KH, KW, ph, pw)
+        ring_ok = (refl and (ph, pw) == (1, 1) and LH >= 3 and LW >= 3 and
+                   (_q("objgan_conv_bank_layout", N, Cout, OH, OW, Cin, T, TH, TW, 0, _MATH["mode"]) & 255) in (1, 3, 4, 5))
         if ring_ok:
             # gradient of the reflect-padded conv without the padded intermediate: interior pixels go straight
             # into dX, the one-pixel border into a small ring buffer that is mirrored back afterwards
             dxl = torch.empty((N, Cin, LH, LW), dtype=_F32, device=g.device)
             ring = torch.empty((N * Cin, 2 * TW + 2 * TH), dtype=_F32, device=g.device)
-            _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, k * k, 1,
+            _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1,
                    dh, dw, st, TH, TW, 1, LH, LW, 1, 1, 0, 0, 0, ring=ring, cache=cacheable)
             _lib.call("objgan_reflect_ring_fold", _p(ring), _p(dxl), N * Cin, LH, LW, _stream())
         else:
             dxl = torch.empty((N, Cin, TH, TW), dtype=_F32, device=g.device)
-            _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, k * k, 1,
+            _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1,
                    dh, dw, st, TH, TW, 1, TH, TW, 1, 1, 0, 0, 0, cache=cacheable)
             if refl:
                 folded = torch.empty((N, Cin, LH, LW), dtype=_F32, device=g.device)
@@ -710,29 +730,25 @@ def _conv_dgrad(g, w, N, Cin, H, W, stride, pad, refl, upsample, cacheable=True)
         if refl:
             raise _lib.ObjganHipError("stride-2 reflect conv is not on the hot path")
         dxl = None
-        if (_THIN4["on"] and k == 4 and pad == 1 and Cin <= 12 and LH == 2 * OH and LW == 2 * OW
+        if (_THIN4["on"] and (KH, KW) == (4, 4) and (ph, pw) == (1, 1) and Cin <= 12 and LH == 2 * OH and LW == 2 * OW
                 and N * OH * OW >= 65536 and float(N) * Cout * OH * OW * 4.0 < 4.0e9):
             dxl = _dgrad_s2_thin(g, w, N, Cout, OH, OW, Cin, cacheable)      # (thin outputs: the four phases in one launch)
         if dxl is None:
-            dxl = _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, k, pad, pad, LH, LW, cacheable)
+            dxl = _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, (KH, KW), ph, pw, LH, LW, cacheable)
         phases = range(2) if dxl is None else ()
         if dxl is None:
             dxl = torch.zeros((N, Cin, LH, LW), dtype=_F32, device=g.device)
-        for ph in phases:
-            khs = [kh for kh in range(k) if (ph + pad - kh) % 2 == 0]
-            PHg = (LH - ph + 1) // 2
-            for pw in range(2):
-                kws = [kw for kw in range(k) if (pw + pad - kw) % 2 == 0]
-                PWg = (LW - pw + 1) // 2
+        for a in phases:
+            PHg = (LH - a + 1) // 2
+            for b in range(2):
+                PWg = (LW - b + 1) // 2
                 if PHg <= 0 or PWg <= 0:
                     continue
-                dh = [(ph + pad - kh) // 2 for kh in khs for kw in kws]
-                dw = [(pw + pad - kw) // 2 for kh in khs for kw in kws]
-                st = [kh * k + kw for kh in khs for kw in kws]
+                dh, dw, st = _taps(KH, KW, a + ph, b + pw, 2)
                 if not st:      # no tap reaches this phase: gradient is zero there
                     dh, dw, st = [0], [0], [-1]
-                _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, k * k, 1,
-                       dh, dw, st, PHg, PWg, 1, LH, LW, 2, 2, ph, pw, 0, y_prezeroed=1, cache=cacheable)
+                _igemm(g, w, None, dxl, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1,
+                       dh, dw, st, PHg, PWg, 1, LH, LW, 2, 2, a, b, 0, y_prezeroed=1, cache=cacheable)
     else:
         raise _lib.ObjganHipError("conv2d backward: stride %d not supported" % stride)
     if upsample:
@@ -885,6 +901,19 @@ def _channel_sum(g, out, N, C, HW):
     _lib.call("objgan_channel_sum", _p(g), _p(out), N, C, HW, _p(ws), _stream())
 
 
+def _act_grad(dy, y, act):
+    """g = dy * act'(y), the gradient w.r.t. the pre-activation output of a convolution with a fused activation, with its
+    partial maxima attached where an fp16x2 launch could read it; dy itself when there is no activation."""
+    if act in (None, "none"):
+        return dy
+    g = torch.empty_like(dy)
+    am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=dy.device) if _amax_wanted(dy.numel()) else None
+    _lib.call("objgan_act_backward", _p(dy), _p(y), _p(g), dy.numel(), _ACT[act], _p(am), _stream())
+    if am is not None:
+        _amax_attach(g, am)
+    return g
+
+
 class _Conv2dFn(torch.autograd.Function):
     """conv2d with the gather-side fusions of the hot path.
 
@@ -918,14 +947,7 @@ class _Conv2dFn(torch.autograd.Function):
         Cout = w.shape[0]
         dy = _c(dy)
         _chk(dy)
-        if act not in (None, "none"):
-            g = torch.empty_like(dy)
-            am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=dy.device) if _amax_wanted(dy.numel()) else None
-            _lib.call("objgan_act_backward", _p(dy), _p(y), _p(g), dy.numel(), _ACT[act], _p(am), _stream())
-            if am is not None:
-                _amax_attach(g, am)
-        else:
-            g = dy
+        g = _act_grad(dy, y, act)
         dx = dw_ = db = None
         if ctx.needs_input_grad[1]:             # (first: inside wgrad_stream_scope it leaves for a side stream at once)
             dw_ = _conv_wgrad(x, g, Cout, k, stride, pad, refl, upsample, sink=_grad_sink(w, (Cout, Cin, k, k)))
@@ -948,7 +970,6 @@ class _Conv2dFn(torch.autograd.Function):
 # arithmetic difference to the lifted form is the pre-summation of filter taps (re-association at
 # the 1e-7 level).  fp32 / bf16x3 math only: the bf16 mode is defined on the rounded ORIGINAL filters.
 _UP_A = ((0., 0., 1.), (0., 1., 1.), (1., 1., 0.), (1., 0., 0.))
-_UP4 = {}           # (weight address, shape) -> [w, _version, epoch, W4]
 
 
 _UP_MAT = {}
@@ -963,26 +984,39 @@ def _up_matrix(device):
     return m
 
 
+def _derived(w, tag, compose):
+    """-> (compose(w.detach()) as a contiguous tensor, cacheable): a tensor derived from the weight w -- the pre-summed
+    up-convolution bank, a slice of the input channels -- kept while the weights are unchanged and rebuilt IN PLACE when
+    they changed, so that the tensor keeps its identity and its packed banks stay cached as well.  A weight is eligible
+    as for the packed banks: its optimizer arena's epoch or its being frozen vouches for it; anything else is recomposed
+    on every call.  An entry is valid for the (`_version`, epoch, address) it was composed from.
+    The cache lives ON the weight object, under `tag` (a process-wide table keyed on the address pinned dead
+    weights and what was derived from them until it overflowed): it dies with the weight."""
+    cache = None
+    if getattr(w, "_og_epoch", None) is not None or not w.requires_grad:
+        try:
+            cache = w.__dict__.setdefault("_og_derived", {})
+        except AttributeError:
+            pass
+    if cache is None:
+        return compose(w.detach()).contiguous(), False
+    stamp = (w._version, _epoch_of(w), w.data_ptr())
+    ent = cache.get(tag)
+    if ent is not None and ent[0] == stamp:
+        return ent[1], True
+    val = compose(w.detach())
+    out = ent[1] if (ent is not None and ent[0][2] == stamp[2]) else torch.empty(val.shape, dtype=_F32, device=w.device)
+    out.copy_(val)                                      # in place: bumps out._version
+    cache[tag] = (stamp, out)
+    return out, True
+
+
 def _up_bank(w):
-    """W4 [Cin, Cout, 4, 4] of a [Cout, Cin, 3, 3] filter bank; rebuilt (in place) only when the
-    weights changed, so that its packed images stay cached as well."""
-    ep = getattr(w, "_og_epoch", None)
-    cacheable = ep is not None or not w.requires_grad
-    A = _up_matrix(w.device)
-    if not cacheable:
-        return torch.einsum("pk,mckl,ql->cmpq", A, w.detach(), A).contiguous(), False
-    key = (w.data_ptr(), tuple(w.shape))
-    ent = _UP4.get(key)
-    epv = ep[0] if ep is not None else -1
-    if ent is not None and ent[0] is w and ent[1] == w._version and ent[2] == epv:
-        return ent[3], True
-    W4 = ent[3] if ent is not None and ent[0] is w else torch.empty(
-        (w.shape[1], w.shape[0], 4, 4), dtype=_F32, device=w.device)
-    W4.copy_(torch.einsum("pk,mckl,ql->cmpq", A, w.detach(), A))      # in place: bumps W4._version
-    if len(_UP4) >= 256:
-        _UP4.clear()
-    _UP4[key] = [w, w._version, epv, W4]
-    return W4, True
+    """W4 [Cin, Cout, 4, 4] of a [Cout, Cin, 3, 3] filter bank -> (W4, cacheable)"""
+    def compose(wd):
+        A = _up_matrix(wd.device)
+        return torch.einsum("pk,mckl,ql->cmpq", A, wd, A)
+    return _derived(w, "up4", compose)
 
 
 def _up_phased_ok(x, w, bias, stride, pad, pad_mode, upsample, act):
@@ -1026,28 +1060,9 @@ class _UpConv3x3Fn(torch.autograd.Function):
 
 
 def _w_slice(w, lo, hi):
-    """contiguous copy of w[:, lo:hi] kept while the weights are unchanged (rebuilt IN PLACE when they changed, so that
-    its packed banks stay cached as well -- `_up_bank` does the same for the pre-summed up-convolution bank): the
-    per-input data gradients of conv2d_cat packed their slice's bank on every call (80 pack launches per training step).
-    The cache lives ON the weight object (a process-wide table keyed on the address pinned dead weights and their
-    slices until it overflowed): it dies with the weight.
-    -> (slice, cacheable)"""
-    ep = getattr(w, "_og_epoch", None)
-    if ep is None and w.requires_grad:
-        return w[:, lo:hi].contiguous(), False
-    try:
-        cache = w.__dict__.setdefault("_og_wslices", {})
-    except AttributeError:
-        return w[:, lo:hi].contiguous(), False
-    ent = cache.get((lo, hi))
-    epv = ep[0] if ep is not None else -1
-    if ent is not None and ent[0] == w._version and ent[1] == epv and ent[3] == w.data_ptr():
-        return ent[2], True
-    ws = ent[2] if (ent is not None and ent[3] == w.data_ptr()) else torch.empty(
-        (w.shape[0], hi - lo) + tuple(w.shape[2:]), dtype=_F32, device=w.device)
-    ws.copy_(w.detach()[:, lo:hi])                      # in place: bumps ws._version
-    cache[(lo, hi)] = [w._version, epv, ws, w.data_ptr()]
-    return ws, True
+    """contiguous copy of w[:, lo:hi] -> (slice, cacheable): the per-input data gradients of conv2d_cat packed their
+    slice's bank on every call (80 pack launches per training step)."""
+    return _derived(w, (lo, hi), lambda wd: wd[:, lo:hi])
 
 
 class _Conv2dCatFn(torch.autograd.Function):
@@ -1076,14 +1091,7 @@ class _Conv2dCatFn(torch.autograd.Function):
         N, C, H, W = x.shape
         dy = _c(dy)
         _chk(dy)
-        if act not in (None, "none"):
-            g = torch.empty_like(dy)
-            am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=dy.device) if _amax_wanted(dy.numel()) else None
-            _lib.call("objgan_act_backward", _p(dy), _p(y), _p(g), dy.numel(), _ACT[act], _p(am), _stream())
-            if am is not None:
-                _amax_attach(g, am)
-        else:
-            g = dy
+        g = _act_grad(dy, y, act)
         n1, n2, nw = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dx1 = dx2 = dw_ = None
         if n1 and n2:
@@ -1111,60 +1119,6 @@ def conv2d(x, w, bias=None, stride=1, pad=0, pad_mode="zeros", upsample=False, a
     return _Conv2dFn.apply(x, w, bias, stride, pad, pad_mode, upsample, act)
 
 
-def _frozen_fwd(x, w, bias, stride, ph, pw, act):
-    """y = act(conv(x, w) + bias) with a frozen rectangular bank, no tape"""
-    N, Cin, H, W = x.shape
-    Cout, Cin2, KH, KW = w.shape
-    if Cin2 != Cin or KH * KW > 32:
-        raise _lib.ObjganHipError("conv2d_frozen: unsupported filter %s" % (tuple(w.shape),))
-    OH = (H + 2 * ph - KH) // stride + 1
-    OW = (W + 2 * pw - KW) // stride + 1
-    y = torch.empty((N, Cout, OH, OW), dtype=_F32, device=x.device)
-    dh = [kh - ph for kh in range(KH) for kw in range(KW)]
-    dw = [kw - pw for kh in range(KH) for kw in range(KW)]
-    # (the frozen encoder's convolutions feed each other through a fused ReLU: the epilogue leaves the maxima)
-    ym = _amax_zeroed(x.device) if (act in ("lrelu", "relu") and _amax_wanted(y.numel())) else None
-    _igemm(x, w, bias, y, N, Cin, H, W, 0, 0, Cout, Cin, KH * KW, 0, dh, dw, list(range(KH * KW)),
-           OH, OW, stride, OH, OW, 1, 1, 0, 0, _ACT[act], ymax=ym)
-    if ym is not None:
-        _amax_attach(y, ym)
-    return y
-
-
-def _frozen_dgrad(g, w, stride, ph, pw, N, Cin, H, W):
-    """gradient w.r.t. the input [N, Cin, H, W] of a frozen convolution given g = dL/d(its pre-activation output)"""
-    Cout, KH, KW = w.shape[0], w.shape[2], w.shape[3]
-    OH, OW = g.shape[2], g.shape[3]
-    T = KH * KW
-    if stride == 1:
-        dx = torch.empty((N, Cin, H, W), dtype=_F32, device=g.device)
-        dh = [ph - kh for kh in range(KH) for kw in range(KW)]
-        dw = [pw - kw for kh in range(KH) for kw in range(KW)]
-        _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, list(range(T)),
-               H, W, 1, H, W, 1, 1, 0, 0, 0)
-    elif stride == 2:
-        dx = _dgrad_s2_phases(g, w, N, Cout, OH, OW, Cin, (KH, KW), ph, pw, H, W)
-        phases = range(2) if dx is None else ()
-        if dx is None:
-            dx = torch.zeros((N, Cin, H, W), dtype=_F32, device=g.device)
-        for a in phases:
-            khs = [kh for kh in range(KH) if (a + ph - kh) % 2 == 0]
-            PHg = (H - a + 1) // 2
-            for b in range(2):
-                kws = [kw for kw in range(KW) if (b + pw - kw) % 2 == 0]
-                PWg = (W - b + 1) // 2
-                if PHg <= 0 or PWg <= 0 or not khs or not kws:
-                    continue
-                dh = [(a + ph - kh) // 2 for kh in khs for kw in kws]
-                dw = [(b + pw - kw) // 2 for kh in khs for kw in kws]
-                st = [kh * KW + kw for kh in khs for kw in kws]
-                _igemm(g, w, None, dx, N, Cout, OH, OW, 0, 0, Cout, Cin, T, 1, dh, dw, st,
-                       PHg, PWg, 1, H, W, 2, 2, a, b, 0, y_prezeroed=1)
-    else:
-        raise _lib.ObjganHipError("conv2d_frozen backward: stride %d not supported" % stride)
-    return dx
-
-
 class _ConvFrozenFn(torch.autograd.Function):
     """Convolution with a FROZEN (non-trainable) rectangular filter bank: forward + input gradient
     only.  Serves the frozen Inception-v3 encoder (1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1 kernels,
@@ -1176,7 +1130,7 @@ class _ConvFrozenFn(torch.autograd.Function):
         if w.requires_grad or (bias is not None and bias.requires_grad):
             raise _lib.ObjganHipError("conv2d_frozen: the filter bank must not require gradients")
         x, w = _c(x), _c(w)
-        y = _frozen_fwd(x, w, bias, stride, ph, pw, act)
+        y = _conv_fwd(x, w, bias, stride, (ph, pw), 0, False, act)      # no tape
         ctx.cfg = (stride, ph, pw, act, tuple(x.shape))
         ctx.save_for_backward(w, y if act not in (None, "none") else None)
         return y
@@ -1187,16 +1141,8 @@ class _ConvFrozenFn(torch.autograd.Function):
         stride, ph, pw, act, (N, Cin, H, W) = ctx.cfg
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None, None, None
-        dy = _c(dy)
-        if act not in (None, "none"):
-            g = torch.empty_like(dy)
-            am = torch.empty(_AMAX_SLOTS, dtype=_F32, device=dy.device) if _amax_wanted(dy.numel()) else None
-            _lib.call("objgan_act_backward", _p(dy), _p(y), _p(g), dy.numel(), _ACT[act], _p(am), _stream())
-            if am is not None:
-                _amax_attach(g, am)
-        else:
-            g = dy
-        return _frozen_dgrad(g, w, stride, ph, pw, N, Cin, H, W), None, None, None, None, None, None
+        g = _act_grad(_c(dy), y, act)
+        return _conv_dgrad(g, w, N, Cin, H, W, stride, (ph, pw), 0, False), None, None, None, None, None, None
 
 
 def conv2d_frozen(x, w, bias=None, stride=1, pad=(0, 0), act=None):
@@ -2747,9 +2693,9 @@ class _PerceptualFn(torch.autograd.Function):
                 x = x.reshape(x.shape[0], -1, 1, 1)                   # x.view(N, -1): NCHW order
             shape_in = tuple(x.shape)
             if kind == "conv":
-                y = _frozen_fwd(x, layer[1], layer[2], 1, 1, 1, "relu")
+                y = _conv_fwd(x, layer[1], layer[2], 1, 1, 0, False, "relu")
             else:
-                y = _frozen_fwd(x, layer[1], layer[2], 1, 0, 0, "relu" if layer[3] else None)
+                y = _conv_fwd(x, layer[1], layer[2], 1, 0, 0, False, "relu" if layer[3] else None)
             need = _q("objgan_l1_tap_ws_doubles", y[:B].numel())
             if ws is None or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.float64, device=x.device)
@@ -2785,7 +2731,7 @@ class _PerceptualFn(torch.autograd.Function):
             relu = kind == "conv" or layer[3]
             g = l1_tap_backward(f, r, None if g is None else _c(g.reshape(f.shape)), coefs[slot:slot + 1], relu)
             pad = 1 if kind == "conv" else 0
-            g = _frozen_dgrad(g, layer[1], 1, pad, pad, B, shape_in[1], shape_in[2], shape_in[3])
+            g = _conv_dgrad(g, layer[1], B, shape_in[1], shape_in[2], shape_in[3], 1, pad, 0, False)
         return pcp_stem_backward(g, ctx.S), None, None
 
 

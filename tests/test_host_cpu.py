@@ -90,6 +90,22 @@ def test_up_bank_cache_follows_weight_updates():
     assert ops._up_bank(q)[1] is False
 
 
+def test_up_bank_dies_with_its_weight():
+    """A tensor derived from a weight (the pre-summed up-convolution bank, a slice of the input channels) is kept on
+    the weight object: when the weight goes, nothing holds what was derived from it."""
+    import gc
+    import weakref
+    from objgan_hip import ops
+    for derive in (ops._up_bank, lambda w: ops._w_slice(w, 3, 15)):
+        w = torch.randn(64, 40, 3, 3)
+        bank, cached = derive(w)
+        assert cached and derive(w)[0] is bank
+        ref = weakref.ref(bank)
+        del bank, w
+        gc.collect()
+        assert ref() is None
+
+
 def test_inception_score_helpers_match_reference(tmp_path):
     """compute_inception_score / negative_log_posterior_probability against the reference's own
     functions (their values stored in tests/golden/reference_host_ref.json; the functions themselves, imported through
