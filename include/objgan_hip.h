@@ -482,13 +482,27 @@ int objgan_moments_finalize(const double* sum, const double* outer, long n, int 
  * writes that blend for all 256 x 256 (image byte, attention byte) pairs.  strip: uint8 [nvis * font_max, Wg, 3],
  * out: uint8 [nvis * (font_max + 2 vis), Wg, 3], Wg = (max_word_num + 2) * (vis + 2); every byte of out is written.
  * ws: objgan_snapshot_ws_doubles doubles (HOST ONLY query; 0 = arguments out of range).  Statistics are combined in a
- * fixed order without atomics: the grid is bit-reproducible. */
+ * fixed order without atomics: the grid is bit-reproducible.
+ * per_panel_norm also selects the shape stage's two forms (reference shape_generation/miscc/utils.py:59-300), both only
+ * with M NULL (fp32 arithmetic on maps of the panel's size; with M the call returns 0):
+ *   2  raw (build_super_images2): byte = trunc(v * 255) in fp32, no minimum or maximum.  Masks are in [0, 1]; outside
+ *      that range the reference's cast is undefined, here the byte saturates to 0 / 255.
+ *   3  per panel, unguarded (the shape stage's build_super_images): (v - min) / (max - min) * 255 per panel; a panel with
+ *      max == min (the reference's 0 / 0 -- every empty box slot) is 0, where mode 1 draws it as it is.
+ * Any other value returns 0.
+ * objgan_mask_to_rgb8: the mask dump of reference shape_generation/trainer.py:389-397.  masks: fp32 planes of HW pixels;
+ * sel (device, N ints, may be NULL: planes 0 .. N - 1): the planes to draw, in any order, repeats allowed -- the caller
+ * vouches that each lies inside `masks`; out: uint8 [N][HW][3].  Per plane byte = trunc((v - min) / (max - min) * 255)
+ * in three separately rounded fp32 operations (denormals kept), replicated to the three channels; max == min (the
+ * reference's NaN cast): zeros.  One workgroup per plane, fixed-order reduction in LDS, no atomics: bit-reproducible.
+ * 16-byte loads when HW % 4 == 0, masks is 16-byte and out 4-byte aligned; scalar accesses otherwise. */
 long objgan_snapshot_ws_doubles(int nvis, int T, int a, int vis);
 int objgan_snapshot_blend_table(unsigned char* table65536);
 int objgan_snapshot_grid(const float* imgs, const float* lr_imgs, const float* attn, const int* counts, const double* M,
                          const unsigned char* strip, unsigned char* out, double* ws, long ws_doubles,
                          int nvis, int T, int a, int vis, int H, int W, int LH, int LW,
                          int max_word_num, int font_max, int per_panel_norm, void* stream);
+int objgan_mask_to_rgb8(const float* masks, const int* sel, unsigned char* out, int N, int HW, void* stream);
 
 /* ---- shape generator training (csrc/convlstm.hip; reference shape_generation/model.py:81-128, miscc/losses.py,
  * datasets.py:99-111).  The ConvLSTM recurrence is split: the input part of the gate convolution runs once over all

@@ -17,6 +17,11 @@
 //                  exact whatever the order; they are still combined in a fixed order, tile by tile, without atomics.
 //                  max == min in the global form: the reference divides 0 by 0 and casts NaN to uint8 (undefined); here
 //                  the panel is written as 0.
+//                  The shape stage's two forms (reference shape_generation/miscc/utils.py:59-300), maps drawn at their own
+//                  size only: raw, trunc(v * 255) in fp32 with no minimum or maximum (build_super_images2; masks are in
+//                  [0, 1], outside it the reference's cast is undefined and the byte saturates to 0 / 255 here), and per
+//                  panel without the guard (build_super_images there): a panel with max == min is the reference's 0 / 0
+//                  and is written as 0, like the global form -- every empty box slot is such a panel.
 //   image panels   nn.Upsample(size=vis, mode='bilinear'), i.e. half-pixel sampling (the arithmetic of
 //                  objgan_bilinear_halfpixel_forward), then (x + 1) / 2 * 255 as three separately rounded fp32 operations
 //                  (the build sets -ffp-contract=off for this file), truncated.
@@ -182,8 +187,14 @@ __device__ __forceinline__ unsigned char snap_image_byte(const float* __restrict
 }
 
 struct SnapGeom {
-    int nvis, P, draw, max_word_num, font_max, vis, H, W, LH, LW, per_panel, fp32_norm;
+    int nvis, P, draw, max_word_num, font_max, vis, H, W, LH, LW, norm, fp32_norm;
 };
+
+// normalisation modes of objgan_snapshot_grid: the panel statistics used and what a panel with max == min becomes
+#define SNAP_NORM_GLOBAL 0            // image-wide min(1, .) / max(0, .); max == min: 0
+#define SNAP_NORM_PANEL 1             // per panel; max == min: the panel as it is
+#define SNAP_NORM_RAW 2               // none: v * 255
+#define SNAP_NORM_PANEL_UNGUARDED 3   // per panel; max == min: 0
 
 __global__ __launch_bounds__(256) void snap_compose_kernel(const float* __restrict__ imgs, const float* __restrict__ lr,
                                                            const double* __restrict__ E, const double* __restrict__ mm,
@@ -234,13 +245,17 @@ __global__ __launch_bounds__(256) void snap_compose_kernel(const float* __restri
             } else {
                 const int j = col - 1;
                 const double v = E[(((long)n * g.P + j) * g.vis + py) * g.vis + px];
-                const double* m2 = mm + 2 * ((long)n * (g.P + 1) + (g.per_panel ? j : g.P));
+                const bool per_panel = g.norm == SNAP_NORM_PANEL || g.norm == SNAP_NORM_PANEL_UNGUARDED;
+                const double* m2 = mm + 2 * ((long)n * (g.P + 1) + (per_panel ? j : g.P));
                 const double mn = m2[0], mx = m2[1];
                 unsigned char att;
-                if (mx == mn) {
-                    // shape form: the map is drawn unnormalised; global form: 0 (the reference's 0 / 0)
-                    att = g.per_panel ? (g.fp32_norm ? snap_trunc_u8((double)((float)v * 255.f)) : snap_trunc_u8(v * 255.0))
-                                      : (unsigned char)0;
+                if (g.norm == SNAP_NORM_RAW) {
+                    att = snap_trunc_u8((double)((float)v * 255.f));         // (fp32 path only: the entry refuses M)
+                } else if (mx == mn) {
+                    // guarded shape form: the map is drawn unnormalised; the other forms: 0 (the reference's 0 / 0)
+                    att = g.norm == SNAP_NORM_PANEL
+                              ? (g.fp32_norm ? snap_trunc_u8((double)((float)v * 255.f)) : snap_trunc_u8(v * 255.0))
+                              : (unsigned char)0;
                 } else if (g.fp32_norm) {
                     float t = (float)v - (float)mn;
                     t = t / ((float)mx - (float)mn);
@@ -264,6 +279,79 @@ __global__ __launch_bounds__(256) void snap_compose_kernel(const float* __restri
         o[0] = b0;
         o[1] = b1;
         o[2] = b2;
+    }
+}
+
+// ---- mask dump (reference shape_generation/trainer.py:389-397): plane -> (v - min) / (max - min) * 255, three channels ----
+#define MASK_THREADS 256
+
+__device__ __forceinline__ unsigned mask_byte(float v, float mn, float den) {
+    float t = v - mn;
+    t = t / den;
+    t = t * 255.f;
+    return (unsigned)snap_trunc_u8((double)t);
+}
+
+// One workgroup per selected plane: pass 1 reduces min / max (per thread, then a fixed-order tree in LDS), pass 2 reads the
+// plane again (L2) and writes the bytes.  VEC: 16-byte loads and 4-byte stores of the 12 bytes of four pixels.
+template <bool VEC>
+__global__ __launch_bounds__(MASK_THREADS) void mask_to_rgb8_kernel(const float* __restrict__ masks,
+                                                                    const int* __restrict__ sel,
+                                                                    unsigned char* __restrict__ out, int HW) {
+    __shared__ float smn[MASK_THREADS], smx[MASK_THREADS];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const float* src = masks + (long)(sel ? sel[n] : n) * HW;
+    unsigned char* dst = out + (long)n * HW * 3;
+    float mn = INFINITY, mx = -INFINITY;
+    if (VEC) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        for (int i = tid; i < HW / 4; i += MASK_THREADS) {
+            const float4 v = s4[i];
+            mn = fminf(fminf(mn, v.x), fminf(v.y, fminf(v.z, v.w)));
+            mx = fmaxf(fmaxf(mx, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
+        }
+    } else {
+        for (int i = tid; i < HW; i += MASK_THREADS) {
+            mn = fminf(mn, src[i]);
+            mx = fmaxf(mx, src[i]);
+        }
+    }
+    smn[tid] = mn;
+    smx[tid] = mx;
+    __syncthreads();
+    for (int s = MASK_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            smn[tid] = fminf(smn[tid], smn[tid + s]);
+            smx[tid] = fmaxf(smx[tid], smx[tid + s]);
+        }
+        __syncthreads();
+    }
+    mn = smn[0];
+    mx = smx[0];
+    const bool flat = !(mx > mn);                                   // max == min: the reference's 0 / 0 -> zeros
+    const float den = mx - mn;
+    if (VEC) {
+        const float4* s4 = reinterpret_cast<const float4*>(src);
+        uint3* d3 = reinterpret_cast<uint3*>(dst);                  // (12 bytes per four pixels, 4-byte aligned)
+        for (int i = tid; i < HW / 4; i += MASK_THREADS) {
+            uint3 w = make_uint3(0u, 0u, 0u);
+            if (!flat) {
+                const float4 v = s4[i];
+                const unsigned a = mask_byte(v.x, mn, den), b = mask_byte(v.y, mn, den);
+                const unsigned c = mask_byte(v.z, mn, den), d = mask_byte(v.w, mn, den);
+                w.x = a * 0x010101u | b << 24;                      // a a a b
+                w.y = b * 0x0101u | c << 16 | c << 24;              // b b c c
+                w.z = c | d * 0x01010100u;                          // c d d d
+            }
+            d3[i] = w;
+        }
+    } else {
+        for (int i = tid; i < HW; i += MASK_THREADS) {
+            const unsigned char b = flat ? (unsigned char)0 : (unsigned char)mask_byte(src[i], mn, den);
+            dst[3 * i] = b;
+            dst[3 * i + 1] = b;
+            dst[3 * i + 2] = b;
+        }
     }
 }
 
@@ -296,6 +384,9 @@ int objgan_snapshot_grid(const float* imgs, const float* lr_imgs, const float* a
     if (lr_imgs && (LH < 1 || LW < 1)) return OG_BAD_ARGS;
     // an expansion needs its matrix and a whole ratio of at least 2; maps drawn as they are have the panel's size
     if (M ? (vis / a < 2) : (vis != a)) return OG_BAD_ARGS;
+    // the shape stage's forms are fp32 arithmetic on maps of the panel's size: no expansion
+    if (per_panel_norm < SNAP_NORM_GLOBAL || per_panel_norm > SNAP_NORM_PANEL_UNGUARDED) return OG_BAD_ARGS;
+    if (M && per_panel_norm >= SNAP_NORM_RAW) return OG_BAD_ARGS;
     const long need = objgan_snapshot_ws_doubles(nvis, T, a, vis);
     if (need <= 0 || ws_doubles < need) return OG_BAD_ARGS;
     const int P = T + 1;
@@ -318,10 +409,23 @@ int objgan_snapshot_grid(const float* imgs, const float* lr_imgs, const float* a
     SnapGeom g;
     g.nvis = nvis; g.P = P; g.draw = P < max_word_num + 1 ? P : max_word_num + 1; g.max_word_num = max_word_num;
     g.font_max = font_max; g.vis = vis; g.H = H; g.W = W; g.LH = LH; g.LW = LW;
-    g.per_panel = per_panel_norm ? 1 : 0; g.fp32_norm = M ? 0 : 1;
+    g.norm = per_panel_norm; g.fp32_norm = M ? 0 : 1;
     const long total = (long)nvis * (font_max + 2 * vis) * (max_word_num + 2) * (vis + 2);
     hipLaunchKernelGGL(snap_compose_kernel, dim3(og_stream_grid(total, 256)), dim3(256), 0, st, imgs, lr_imgs, E, mm, strip,
                        counts, out, g);
+    return og_launch_status();
+}
+
+int objgan_mask_to_rgb8(const float* masks, const int* sel, unsigned char* out, int N, int HW, void* stream) {
+    OG_ENTRY();
+    if (!masks || !out || N < 1 || HW < 1 || (long)N * HW * 3 > 0x7fffffffL) return OG_BAD_ARGS;
+    hipStream_t st = (hipStream_t)stream;
+    // every selected plane starts a multiple of HW floats behind `masks`, every output plane 3 HW bytes behind `out`
+    const bool vec = HW % 4 == 0 && ((uintptr_t)masks & 15) == 0 && ((uintptr_t)out & 3) == 0;
+    if (vec)
+        hipLaunchKernelGGL(mask_to_rgb8_kernel<true>, dim3(N), dim3(MASK_THREADS), 0, st, masks, sel, out, HW);
+    else
+        hipLaunchKernelGGL(mask_to_rgb8_kernel<false>, dim3(N), dim3(MASK_THREADS), 0, st, masks, sel, out, HW);
     return og_launch_status();
 }
 

@@ -335,14 +335,15 @@ def decode_rgb(img_bytes):
     return torch.from_numpy(np.array(img, dtype=np.uint8))
 
 
-def get_imgs(img_bytes, imsize, normalize=None):
+def get_imgs(img_bytes, imsize, normalize=None, branch_num=None):
     """Decode and resize to every branch size (torchvision Resize((s, s)) on a PIL image is PIL's
-    bilinear resize with its built-in antialiasing)."""
+    bilinear resize with its built-in antialiasing).  branch_num: how many of the sizes in `imsize`
+    (default cfg.TREE.BRANCH_NUM; the shape stage reads one)."""
     from PIL import Image
     img = Image.open(io.BytesIO(img_bytes)).convert('RGB')
     norm = normalize if normalize is not None else _normalize_to_tensor
     ret = []
-    for i in range(cfg.TREE.BRANCH_NUM):
+    for i in range(cfg.TREE.BRANCH_NUM if branch_num is None else branch_num):
         ret.append(norm(img.resize((imsize[i], imsize[i]), Image.BILINEAR)))
     return ret
 

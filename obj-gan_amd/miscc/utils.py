@@ -53,13 +53,14 @@ def caption_font(size=50):
     return fnt
 
 
-def drawCaption(convas, captions, ixtoword, vis_size, off1=2, off2=2):
-    """Draw '%d:%s' % (j, word[:6]) labels of every caption onto the uint8 canvas, caption i at row i * FONT_MAX, word
-    j at column (j + off1) * (vis_size + off2) (reference utils.py:36-56; text past the canvas is clipped).
-    -> (PIL image, list of word lists)."""
+def drawCaption(convas, captions, ixtoword, vis_size, off1=2, off2=2, font_max=FONT_MAX, font_size=50):
+    """Draw '%d:%s' % (j, word[:6]) labels of every caption onto the uint8 canvas, caption i at row i * font_max, word
+    j at column (j + off1) * (vis_size + off2) (reference utils.py:36-56; text past the canvas is clipped).  font_max /
+    font_size: the row pitch and the font's size, which the shape stage's drawCaption takes as arguments (reference
+    shape_generation/miscc/utils.py:35-56).  -> (PIL image, list of word lists)."""
     from PIL import Image, ImageDraw
     img_txt = Image.fromarray(convas)
-    fnt = caption_font(50)
+    fnt = caption_font(font_size)
     d = ImageDraw.Draw(img_txt)
     caps = _host(captions)
     sentence_list = []
@@ -69,8 +70,8 @@ def drawCaption(convas, captions, ixtoword, vis_size, off1=2, off2=2):
             if caps[i, j] == 0:
                 break
             word = ixtoword[int(caps[i, j])].encode('ascii', 'ignore').decode('ascii')
-            if fnt is not None and i * FONT_MAX < convas.shape[0]:
-                d.text(((j + off1) * (vis_size + off2), i * FONT_MAX), '%d:%s' % (j, word[:6]), font=fnt,
+            if fnt is not None and i * font_max < convas.shape[0]:
+                d.text(((j + off1) * (vis_size + off2), i * font_max), '%d:%s' % (j, word[:6]), font=fnt,
                        fill=(255, 255, 255, 255))
             sentence.append(word)
         sentence_list.append(sentence)

@@ -97,6 +97,7 @@ SIGNATURES = {
     "objgan_jpeg_decode": [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_long, _ptr, _ptr, _ptr],
     "objgan_snapshot_blend_table": [_ptr],
     "objgan_snapshot_grid": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_long] + [_c_int] * 11 + [_ptr],
+    "objgan_mask_to_rgb8": [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr],
     "objgan_convlstm_cell_forward": [_ptr] * 7 + [_c_int] * 3 + [_c_long] * 2 + [_ptr],
     "objgan_convlstm_cell_backward": [_ptr] * 8 + [_c_int] * 3 + [_c_long] * 2 + [_ptr],
     "objgan_box_max_forward": [_ptr, _ptr, _ptr, _c_int, _c_int, _c_long, _ptr],

@@ -1971,14 +1971,26 @@ def paste_blend_table():
     return table
 
 
+SNAPSHOT_NORMS = {"global": 0, "panel": 1, "raw": 2, "panel_unguarded": 3}
+
+
 def snapshot_grid(imgs, attn_maps, att_sze, text_strip, lr_imgs=None, max_word_num=12, font_max=50, nvis=8,
-                  per_panel_norm=False):
-    """The caption / attention grid of reference miscc/utils.py:59-182 (per_panel_norm: :184-306) for the first `nvis`
-    images, composed on the device: uint8 [nvis * (font_max + 2 vis), (max_word_num + 2) * (vis + 2), 3] with
-    vis = 272 when att_sze == 17 and the image size otherwise.  imgs / lr_imgs [B, 3, h, w] in [-1, 1]; attn_maps
-    [B, T, att_sze, att_sze] (any shape that views as that), or a list of per-image [1, T_i, att_sze, att_sze] tensors (the
-    per-caption maps of the DAMSM word loss); text_strip: uint8 device tensor [nvis * font_max, width, 3], the caption
-    rows drawn by the caller.  No device->host synchronisation."""
+                  per_panel_norm=None, norm=None):
+    """The caption / attention grid of reference miscc/utils.py:59-182 for the first `nvis` images, composed on the
+    device: uint8 [nvis * (font_max + 2 vis), (max_word_num + 2) * (vis + 2), 3] with vis = 272 when att_sze == 17 and the
+    image size otherwise.  imgs / lr_imgs [B, 3, h, w] in [-1, 1]; attn_maps [B, T, att_sze, att_sze] (any shape that views
+    as that), or a list of per-image [1, T_i, att_sze, att_sze] tensors (the per-caption maps of the DAMSM word loss);
+    text_strip: uint8 device tensor [nvis * font_max, width, 3], the caption rows drawn by the caller.
+    norm: 'global' (default; minimum / maximum over the image's panels), 'panel' (:184-306, a constant panel drawn as it
+    is), and the shape stage's 'raw' (v * 255) and 'panel_unguarded' (a constant panel is 0) -- these two only for maps of
+    the panel's own size.  per_panel_norm=True / False is the older spelling of 'panel' / 'global'.
+    No device->host synchronisation."""
+    if norm is None:
+        norm = "panel" if per_panel_norm else "global"
+    elif per_panel_norm is not None:
+        raise _lib.ObjganHipError("snapshot_grid: give norm= or per_panel_norm=, not both")
+    if norm not in SNAPSHOT_NORMS:
+        raise _lib.ObjganHipError("snapshot_grid: norm is one of %s (got %r)" % (sorted(SNAPSHOT_NORMS), norm))
     as_list = isinstance(attn_maps, (list, tuple))
     _chk(imgs, lr_imgs, *(attn_maps if as_list else (attn_maps,)))
     if not (torch.is_tensor(text_strip) and text_strip.is_cuda and text_strip.dtype == torch.uint8):
@@ -2015,12 +2027,49 @@ def snapshot_grid(imgs, attn_maps, att_sze, text_strip, lr_imgs=None, max_word_n
     imgs = _c(imgs.detach())
     lr = _c(lr_imgs.detach()) if lr_imgs is not None else None
     LH, LW = (int(lr.shape[2]), int(lr.shape[3])) if lr is not None else (0, 0)
+    if ratio > 1 and SNAPSHOT_NORMS[norm] >= 2:
+        raise _lib.ObjganHipError("snapshot_grid: norm=%r draws maps at their own size (maps %d x %d, panels %d x %d)"
+                                  % (norm, a, a, vis, vis))
     M = _expansion_matrix_dev(a, vis, imgs.device) if ratio > 1 else None
     nws = _q("objgan_snapshot_ws_doubles", nvis, T, a, vis)
     ws = torch.empty(nws, dtype=torch.float64, device=imgs.device)
     out = torch.empty((nvis * (font_max + 2 * vis), width, 3), dtype=torch.uint8, device=imgs.device)
     _lib.call("objgan_snapshot_grid", _p(imgs), _p(lr), _p(attn), _p(counts), _p(M), _p(_c(text_strip)), _p(out), _p(ws), nws,
-              nvis, T, a, vis, H, W, LH, LW, mw, font_max, 1 if per_panel_norm else 0, _stream())
+              nvis, T, a, vis, H, W, LH, LW, mw, font_max, SNAPSHOT_NORMS[norm], _stream())
+    return out
+
+
+def mask_to_rgb8(masks, sel=None):
+    """The mask dump of reference shape_generation/trainer.py:389-397 on the device: fp32 planes masks [..., h, w] ->
+    uint8 [N, h, w, 3], plane by plane (v - min) / (max - min) * 255 truncated and replicated to three channels; a
+    constant plane (the reference's 0 / 0) is zeros.  sel: the flat indices of the N planes to draw, in any order,
+    repeats allowed (None: all planes).  Give it as a host sequence: it is checked there and uploaded through pinned
+    memory; a device tensor is checked too, at the price of a synchronisation."""
+    _chk(masks)
+    if masks.dim() < 2:
+        raise _lib.ObjganHipError("mask_to_rgb8: masks are [..., h, w]")
+    h, w = int(masks.shape[-2]), int(masks.shape[-1])
+    planes = masks.numel() // max(h * w, 1)
+    if h * w < 1 or planes < 1:
+        raise _lib.ObjganHipError("mask_to_rgb8: no pixels in masks of shape %s" % (tuple(masks.shape),))
+    m = _c(masks.detach())
+    sel_dev, N = None, planes
+    if sel is not None:
+        if torch.is_tensor(sel) and sel.is_cuda:
+            lo, hi, N = int(sel.min()), int(sel.max()), int(sel.numel())
+            sel_dev = _c(sel.to(torch.int32).reshape(-1))
+        else:
+            import numpy as np
+            host = np.asarray(sel.numpy() if torch.is_tensor(sel) else sel, dtype=np.int64).reshape(-1)
+            N = int(host.size)
+            if N < 1:
+                raise _lib.ObjganHipError("mask_to_rgb8: empty selection")
+            lo, hi = int(host.min()), int(host.max())
+            sel_dev = torch.from_numpy(host.astype(np.int32)).pin_memory().to(m.device, non_blocking=True)
+        if lo < 0 or hi >= planes:
+            raise _lib.ObjganHipError("mask_to_rgb8: selection %d .. %d outside the %d planes" % (lo, hi, planes))
+    out = torch.empty((N, h, w, 3), dtype=torch.uint8, device=m.device)
+    _lib.call("objgan_mask_to_rgb8", _p(m), _p(sel_dev), _p(out), N, h * w, _stream())
     return out
 
 

@@ -5,7 +5,8 @@ fm_rois, instance masks, pooled mask, box maps at 64x64 and 16x16, num_rois), `<
 `captions.pickle` (for the word index of the category names) and `categories.txt` -- and never builds them: making the
 annotation pickle from the COCO json needs pycocotools and skimage and stays an offline step.
 
-An item is the reference's minus the image (only its display path reads it), and with the box maps in their compact
+An item is the reference's minus the image (only its display path reads it: `images_for` fetches the images of a
+batch's keys from `<split>_imgs.bigfile` when a grid is drawn), and with the box maps in their compact
 form: the raw per-box maps [BOXES_NUM, S, S] and the category of each slot.  `prepare_data` uploads those kilobytes and
 writes the one-hot `bbox_maps_fwd` / `bbox_maps_bwd` [B, R, nbf, S, S] on the device (`ops.boxmaps_onehot`);
 `get_hmaps_rois` is the reference's host form of the same tensors.  The reference's quirk is kept: the backward
@@ -92,6 +93,7 @@ class TextDataset(data.Dataset):
         self.class_id = self.load_class_id(os.path.join(data_dir, split), len(self.filenames))
         self.cats_dict, self.cats_index_dict = self.load_cats()
         self.insanns_dict = self.load_anns_data(data_dir, split)
+        self._img_bytes = self._img_index = None
 
     @staticmethod
     def load_filenames(data_dir, split):
@@ -137,6 +139,31 @@ class TextDataset(data.Dataset):
                           "shape_generation/datasets.py (pycocotools + skimage) and only read here" % path)
         with open(path, 'rb') as f:
             return pickle.load(f)[0]
+
+    # ---- the images: read by the display path only, so never part of an item ----
+    def imgs_path(self):
+        return os.path.join(self.data_dir, '%s_imgs.bigfile' % self.split)
+
+    def __getstate__(self):
+        # (a loader worker gets the data set without the open bigfile: a memory map does not pickle)
+        return dict(self.__dict__, _img_bytes=None, _img_index=None)
+
+    def has_images(self):
+        """whether <split>_imgs.bigfile exists (it is never written from here)"""
+        return os.path.isfile(self.imgs_path())
+
+    def images_for(self, keys):
+        """-> [n, 3, imsize, imsize] in [-1, 1]: the images of `keys` as the reference's item holds them (datasets.py:74-88:
+        Pillow's bilinear resize, ToTensor, Normalize 0.5), read from <split>_imgs.bigfile, which is opened at the first
+        call"""
+        from miscc import load
+        if self._img_bytes is None:
+            if not self.has_images():
+                raise IOError("%s not found" % self.imgs_path())
+            self._img_bytes = load.load_imgs_data(self.data_dir, self.split, self.filenames)
+            self._img_index = {k: i for i, k in enumerate(self.filenames)}
+        return torch.stack([load.get_imgs(self._img_bytes[self._img_index[k]], [self.imsize], branch_num=1)[0]
+                            for k in keys])
 
     def __getitem__(self, index):
         key = self.filenames[index]

@@ -5,7 +5,9 @@ dataset)` with `build_models`, `define_optimizers`, `save_model`, `train`; the b
 `train_step`, usable on its own.  What is built is the whole step -- generator, instance and global discriminator, the
 perceptual term on the frozen VGG-19-bn (PCP_LAMBDA != 0: the network is loaded once from
 <DATA_DIR>/pretrained/vgg19_bn-c79401a0.pth, a missing file is refused before any work), gradient clipping, Adam, the
-EMA copy, the checkpoints and `Score/scores_N.txt`.  NOT built: the DISPLAY_INTERVAL grids.
+EMA copy, the checkpoints, `Score/scores_N.txt`, the DISPLAY_INTERVAL grids `Image/{G,D,G2,D2}_average_<iter>.png`
+(`save_img_results`, trainer.py:149-206) and `sampling` (trainer.py:316-401), the dump of one mask PNG per test image.
+NOT built: data-parallel training over several GPUs.
 
 Results-preserving differences:
   * parameters, gradients and Adam moments of each network live in flat arenas (`trainer.ParamArena`): one Adam launch
@@ -15,7 +17,12 @@ Results-preserving differences:
     over the boxes is taken once per step;
   * discriminator weights are frozen during the generator step (the reference zeroes those gradients before use);
   * nothing is read back from the device unless the step prints or a checkpoint is written; pcp_score accumulates on
-    the device and is read once per epoch (it is never reset between epochs, as in the reference).
+    the device and is read once per epoch (it is never reset between epochs, as in the reference);
+  * the grids and the mask dump are composed on the device (`miscc.shape_utils`, `ops.mask_to_rgb8`): only finished
+    uint8 arrays leave it.  Defined where the reference is not: a constant panel or mask (its 0 / 0) is 0, an image
+    without a box is skipped by `sampling` and counted, and a grid shows min(8, batch size) images;
+  * the images, which only the grids show, are read from `<split>_imgs.bigfile` when a grid is drawn; a data directory
+    without that file trains without grids, after one notice.
 Kept as it is: the three optimizers are re-created at every epoch (trainer.py:226), so their moments and step counts
 start from zero each epoch; lr_rate *= 0.98 for epochs above 50.
 """
@@ -23,6 +30,7 @@ import ntpath
 import os
 import time
 
+import numpy as np
 import torch
 
 from miscc.config import cfg
@@ -34,6 +42,9 @@ from objgan_hip import ops
 import shapeDataset
 
 EMA_DECAY = 0.999
+# zlib level of the PNG files (Pillow's default is 6).  The pixels are the contract, not the file bytes: a grid of 2.8 MB
+# takes 65 ms to encode at level 6 and 46 ms at level 1 for files of the same size within 2 % (LAB.md section 23).
+PNG_COMPRESS_LEVEL = 1
 
 
 class ClippedArenaAdam(object):
@@ -82,15 +93,20 @@ def path_leaf(path):
 class condGANTrainer(object):
     def __init__(self, output_dir, data_loader, dataset, device=None):
         self.model_dir = os.path.join(output_dir, 'Model')
+        self.image_dir = os.path.join(output_dir, 'Image')
         self.score_dir = os.path.join(output_dir, 'Score')
         if cfg.TRAIN.FLAG:
             mkdir_p(self.model_dir)
+            mkdir_p(self.image_dir)
             mkdir_p(self.score_dir)
         self.device = torch.device(device if device is not None else ("cuda:0" if cfg.CUDA else "cpu"))
         self.batch_size = cfg.TRAIN.BATCH_SIZE
         self.max_epoch = cfg.TRAIN.MAX_EPOCH
         self.snapshot_interval = cfg.TRAIN.SNAPSHOT_INTERVAL
         self.print_interval = cfg.TRAIN.PRINT_INTERVAL
+        self.display_interval = int(cfg.TRAIN.DISPLAY_INTERVAL)
+        self.dataset = dataset
+        self.ixtoword = getattr(dataset, 'ixtoword', None)
         self.cats_dict = dataset.cats_dict
         self.cats_index_dict = dataset.cats_index_dict
         self.num_classes = len(self.cats_index_dict)
@@ -99,6 +115,7 @@ class condGANTrainer(object):
         self.clip_norm = float(cfg.TRAIN.get("RNN_GRAD_CLIP", 0.25))
         self.netG = None
         self.vgg = None
+        self._png_pool, self._png_jobs = None, []
 
     # ---- networks ----
     def build_models(self):
@@ -201,6 +218,129 @@ class condGANTrainer(object):
             torch.save({k: v.detach().cpu().clone() for k, v in net.state_dict().items()},
                        '%s/%s' % (self.model_dir, leaf))
 
+    # ---- snapshot grids (reference trainer.py:149-206) ----
+    @torch.no_grad()
+    def save_img_results(self, batch, noise, gen_iterations, name='current', imgs=None, wait=True):
+        """Image/{G,D,G2,D2}_<name>_<n>.png: the generated (G) and the real (D) masks of the first min(8, B) images of
+        `batch` beside their images, every panel normalised by its own range (G_, D_) and raw (G2_, D2_).  The generator
+        runs with the EMA weights swapped in through the arena; the live weights, the moments and the noise stream are
+        as before afterwards.  imgs: [>= nvis, 3, S, S] in [-1, 1] (None: read from the data set by the batch's keys).
+        Only the four finished uint8 grids leave the device.  The PNG files are encoded by worker threads (the encoder
+        leaves the interpreter free): wait=False returns once the grids are on the host and leaves the files to
+        `finish_images`, which the next call and the end of `train` run.  -> the paths written."""
+        from PIL import Image
+        from miscc.shape_utils import build_super_images, build_super_images2, caption_strip
+        font_max, font_size, mw = 20, 12, int(cfg.ROI.BOXES_NUM)
+        nvis = min(8, int(noise.size(0)))
+        a = self.arenaG
+        backup = a.flat.clone()
+        a.flat.copy_(self.avg_param_G)
+        a.epoch[0] += 1                                   # (the packed filter banks are keyed on it)
+        try:
+            # only the images that are shown: the generator couples nothing across the images of a batch
+            fake_hmaps = self.netG(noise[:nvis], batch["bbox_maps_fwd"][:nvis], batch["bbox_maps_bwd"][:nvis],
+                                   batch["bbox_fmaps"][:nvis])
+        finally:
+            a.flat.copy_(backup)
+            a.epoch[0] += 1
+            ops.repack_arena(a.epoch)
+        S = int(fake_hmaps.size(-1))
+        if imgs is None:
+            imgs = self.dataset.images_for(batch["keys"][:nvis])
+        imgs = imgs[:nvis].to(self.device, torch.float32)
+        captions = np.zeros((nvis, mw), np.int64)
+        rois, num_rois = np.asarray(batch["rois"]), np.asarray(batch["num_rois"]).reshape(-1)
+        for b in range(nvis):
+            for r in range(min(int(num_rois[b]), mw)):
+                captions[b, r] = self.cats_dict[int(rois[b, r, 4])][0]
+        strip = caption_strip(captions, self.ixtoword, nvis, S, font_max, font_size, mw, self.device)
+        self.finish_images()
+        if self._png_pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._png_pool = ThreadPoolExecutor(max_workers=4)
+        paths = []
+        for tag, fn, maps in (("G", build_super_images, fake_hmaps), ("D", build_super_images, batch["hmaps"]),
+                              ("G2", build_super_images2, fake_hmaps), ("D2", build_super_images2, batch["hmaps"])):
+            grid, _ = fn(imgs, captions, self.ixtoword, maps[:nvis], S, lr_imgs=None, font_max=font_max,
+                         font_size=font_size, max_word_num=mw, strip=strip)
+            paths.append('%s/%s_%s_%d.png' % (self.image_dir, tag, name, gen_iterations))
+            self._png_jobs.append(self._png_pool.submit(Image.fromarray(grid).save, paths[-1],
+                                                        compress_level=PNG_COMPRESS_LEVEL))
+        if wait:
+            self.finish_images()
+        return paths
+
+    def finish_images(self):
+        """wait for the PNG files of earlier display calls; an error of a writer is raised here"""
+        jobs, self._png_jobs = self._png_jobs, []
+        for job in jobs:
+            job.result()
+
+    def display_ready(self):
+        """whether train() can draw the grids: an interval above 0 and a data set that has its images; says once why not"""
+        if self.display_interval <= 0:
+            return False
+        has = getattr(self.dataset, 'has_images', None)
+        if has is not None and has():
+            return True
+        print('No %s: this run trains without the DISPLAY_INTERVAL grids (they show the images).'
+              % (self.dataset.imgs_path() if has is not None else 'image file in this data set'))
+        return False
+
+    # ---- one mask PNG per image (reference trainer.py:316-401) ----
+    @torch.no_grad()
+    def sampling(self, split_dir, noise=None, all_boxes=False):
+        """Load cfg.TRAIN.NET_G and write <NET_G without .pth>/<split>/single/<key>_<word>.png for every image of the
+        loader's whole batches: the mask of its first box, (v - min) / (max - min) * 255 on three channels, <word> the
+        first word of the box's category.  all_boxes (an extension): every box r, as <key>_<r>_<word>.png.  Per batch one
+        generator forward, one `ops.mask_to_rgb8` launch, one device-to-host copy.  An image without a box (the
+        reference: IndexError) is skipped; the count is printed.  noise: [B, BOXES_NUM, 4 * classes] used for every
+        batch, or a sequence of such tensors, one per batch (None: drawn per batch).  -> (files written, images skipped)"""
+        from PIL import Image
+        if cfg.TRAIN.NET_G == '':
+            print('Error: the path for models is not found!')
+            return 0, 0
+        if split_dir == 'test':
+            split_dir = 'valid'
+        netG = SHP_G_NET(self.num_classes)
+        netG.load_state_dict(torch.load(cfg.TRAIN.NET_G, map_location="cpu"))
+        netG = netG.to(self.device).eval()
+        print('Load G from: ', cfg.TRAIN.NET_G)
+        model_dir = cfg.TRAIN.NET_G
+        save_dir = '%s/%s' % (model_dir[:model_dir.rfind('.pth')], split_dir)
+        mkdir_p(save_dir)
+        z = torch.empty(self.batch_size, cfg.ROI.BOXES_NUM, self.num_classes * 4, device=self.device)
+        written = skipped = 0
+        for step, data in enumerate(self.data_loader):
+            if step % 100 == 0:
+                print('step: ', step)
+            num = [int(n) for n in data[7]]
+            skipped += sum(1 for n in num if n < 1)
+            if max(num) < 1:
+                continue
+            batch = shapeDataset.prepare_data(data, self.device, self.num_classes)
+            R = batch["max_num_roi"]
+            if noise is None:
+                z.normal_(0, 1)
+                zz = z
+            else:
+                zz = (noise if torch.is_tensor(noise) else noise[step]).to(self.device)
+            fake_hmaps = netG(zz[:, :R], batch["bbox_maps_fwd"], batch["bbox_maps_bwd"], batch["bbox_fmaps"])
+            todo = [(b, r) for b, n in enumerate(num) for r in range(n if all_boxes else min(n, 1))]
+            rgb = ops.mask_to_rgb8(fake_hmaps, [b * R + r for b, r in todo]).cpu().numpy()
+            for im, (b, r) in zip(rgb, todo):
+                stem = '%s/single/%s' % (save_dir, batch["keys"][b])
+                folder = stem[:stem.rfind('/')]
+                if not os.path.isdir(folder):
+                    print('Make a new folder: ', folder)
+                    mkdir_p(folder)
+                word = self.ixtoword[self.cats_dict[int(batch["rois"][b, r, 4])][0]].encode('ascii', 'ignore').decode('ascii')
+                Image.fromarray(im).save(('%s_%d_%s.png' % (stem, r, word)) if all_boxes else '%s_%s.png' % (stem, word),
+                                         compress_level=PNG_COMPRESS_LEVEL)
+                written += 1
+        print('sampling: %d files in %s/single, %d images without a box skipped' % (written, save_dir, skipped))
+        return written, skipped
+
     def write_score(self, epoch):
         """the epoch's one host read of the accumulated perceptual score (reference trainer.py:304-308; never reset)"""
         pcp_score = float(self.pcp_score)
@@ -212,11 +352,18 @@ class condGANTrainer(object):
     # ---- the loop ----
     def train(self):
         start_epoch = self.build_models()[3]
+        gap = "Not built here: data-parallel training over several GPUs (--gpu '0,1' uses the first device)."
         if self.vgg is None:
-            print('Not built here: the DISPLAY_INTERVAL image grids.  PCP_LAMBDA = 0: this run leaves the perceptual term '
-                  'out (gpcp_loss and pcp_score stay 0).')
+            print(gap + '  PCP_LAMBDA = 0: this run leaves the perceptual term out (gpcp_loss and pcp_score stay 0).')
         else:
-            print('Not built here: the DISPLAY_INTERVAL image grids.')
+            print(gap)
+        display = self.display_ready()
+        fixed_noise = torch.empty_like(self.noise)
+        if display:
+            # drawn once, from a generator of its own: the training noise is the same stream with and without grids
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(torch.initial_seed())
+            fixed_noise.normal_(0, 1, generator=gen)
         gen_iterations = 0
         lr_rate = 1
         for epoch in range(start_epoch, self.max_epoch):
@@ -225,8 +372,12 @@ class condGANTrainer(object):
                 lr_rate *= 0.98
             self.define_optimizers(lr_rate)
             for step, data in enumerate(self.data_loader, 1):
-                out = self.train_step(shapeDataset.prepare_data(data, self.device, self.num_classes))
+                batch = shapeDataset.prepare_data(data, self.device, self.num_classes)
+                out = self.train_step(batch)
                 gen_iterations += 1
+                if display and gen_iterations % self.display_interval == 0:
+                    self.save_img_results(batch, fixed_noise[:, :batch["max_num_roi"]], gen_iterations, name='average',
+                                          wait=False)
                 if gen_iterations % self.print_interval == 0:
                     vals = {k: float(out[k]) for k in ("errINSD", "errGLBD", "insg_loss", "glbg_loss", "gpcp_loss")}
                     elapsed = time.time() - start_t
@@ -241,3 +392,4 @@ class condGANTrainer(object):
             if epoch % self.snapshot_interval == 0:
                 self.save_model(epoch)
         self.save_model(self.max_epoch)
+        self.finish_images()

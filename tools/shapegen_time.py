@@ -20,7 +20,16 @@ full-width weights.  Per batch size, alternating runs on the same seeded batch:
   * the convolutions inside the term: algorithmic FLOP (forward on 2 B images, data gradient on B, Linears included)
     over the term's time minus the replayed kernels' time (the five pool passes stay in that remainder).
 
+`--display`: the cost of the pictures at the reference batch of 40.  One `save_img_results` call (wall clock around
+the call with a device synchronisation on both sides, the four PNG files written to a temporary directory) per PNG
+compression level; five training steps with and without one display call behind them, as `train` issues it (the files
+left to the worker threads); the call split into its parts -- the generator forward with the EMA swap, the caption strip, the four grid
+compositions with their device-to-host copies, the four PNG encodings -- beside the training step with PCP_LAMBDA 0 and
+10 (seeded full-width VGG unless `--vgg-weights`), decoding eight 640 x 480 JPEGs the way `images_for` does, and the
+rate of `sampling` over `--sample-batches` synthetic batches, files included.
+
     python tools/shapegen_time.py [--B 40] [--R 10] [--nbf 80] [--steps 10] [--warmup 3] [--out FILE] [--step-only]
+    python tools/shapegen_time.py --display [--steps 5] [--warmup 2] [--sample-batches 10] [--out FILE]
     python tools/shapegen_time.py --pcp [--vgg-weights FILE] [--pcp-batches 40,16] [--steps 5] [--warmup 2] [--out FILE]
 """
 import argparse
@@ -50,8 +59,13 @@ def inputs(B, R, nbf, dev, seed=0):
     fwd, bwd = ops.boxmaps_onehot(raw.to(dev), cats.to(dev), num.to(torch.int32).to(dev), R, nbf)
     fmaps = torch.nn.functional.max_pool2d(raw[:, :R], 4).to(dev)
     real = (torch.rand(B, R, 1, 64, 64, generator=g) * raw[:, :R].unsqueeze(2)).to(dev)
+    rois = torch.cat([xy, wh, cats.view(B, 10, 1).long(), torch.zeros(B, 10, 1, dtype=torch.long)], 2).double()
     return {"max_num_roi": R, "bbox_maps_fwd": fwd, "bbox_maps_bwd": bwd, "bbox_fmaps": fmaps.contiguous(),
-            "hmaps": real, "pooled_hmaps": real.max(1)[0]}
+            "hmaps": real, "pooled_hmaps": real.max(1)[0], "rois": rois.numpy(), "num_rois": num,
+            "keys": ["img_%05d" % i for i in range(B)],
+            # the collated item tuple of shapeDataset (what `sampling` takes from its loader)
+            "item": (real.max(1)[0][:, 0].cpu(), torch.zeros(B, 10, 64, 64), raw, cats, torch.nn.functional.max_pool2d(raw, 4),
+                     rois, rois / 4.0, num, torch.arange(B), ["img_%05d" % i for i in range(B)])}
 
 
 def timed(fn, steps, warmup):
@@ -194,6 +208,122 @@ def pcp_main(a, dev):
     return res
 
 
+def wall(fn, steps, warmup):
+    """host wall clock per call in ms, the device drained on both sides"""
+    import time
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def display_main(a, dev):
+    """--display: see the module docstring"""
+    import io
+    import tempfile
+    import numpy as np
+    from PIL import Image
+    import model
+    import shape_trainer
+    from miscc import load, shape_utils
+    from miscc.config import cfg
+    from objgan_hip import ops
+    B, R, nbf = a.B, a.R, a.nbf
+    cfg.TRAIN.BATCH_SIZE, cfg.TRAIN.FLAG, cfg.GAN.R_NUM = B, True, 1
+    cfg.TRAIN.SMOOTH.INS_LAMBDA, cfg.TRAIN.SMOOTH.GLB_LAMBDA, cfg.TRAIN.SMOOTH.PCP_LAMBDA = 1.0, 1.0, 0.0
+    ds = type("DS", (), {"cats_dict": {i: [1 + i % 7] for i in range(nbf)}, "cats_index_dict": {i: i for i in range(nbf)},
+                         "ixtoword": {i: "word%d" % i for i in range(8)}})()
+    torch.manual_seed(0)
+    out_dir = tempfile.mkdtemp(prefix="shapegen_time_")
+    t = shape_trainer.condGANTrainer(out_dir, None, ds, device=dev)
+    t.build_models()
+    t.define_optimizers(1.0)
+    batch = inputs(B, R, nbf, dev)
+    imgs = torch.tanh(torch.randn(B, 3, 64, 64, device=dev))
+    z = torch.randn(B, R, 4 * nbf, device=dev)
+    res = {"mode": "display", "B": B, "R": R, "nbf": nbf, "steps": a.steps, "warmup": a.warmup, "conv_math": ops.get_conv_math()}
+    res["step_ms_lambda_0"] = [timed(lambda: t.train_step(batch), a.steps, a.warmup) for _ in range(a.rounds)]
+    sd = torch.load(a.vgg_weights, map_location="cpu") if a.vgg_weights else seeded_vgg_state()
+    t.vgg = model.VGG(sd).to(dev)
+    del sd
+    cfg.TRAIN.SMOOTH.PCP_LAMBDA = 10.0
+    res["step_ms_lambda_10"] = [timed(lambda: t.train_step(batch), a.steps, a.warmup) for _ in range(a.rounds)]
+    cfg.TRAIN.SMOOTH.PCP_LAMBDA = 0.0
+    t.vgg = None
+    torch.cuda.empty_cache()
+    res["save_img_results_ms"] = {}
+    for level in (6, 1):
+        shape_trainer.PNG_COMPRESS_LEVEL = level
+        res["save_img_results_ms"]["png_level_%d" % level] = [
+            wall(lambda: t.save_img_results(batch, z, 5, name="average", imgs=imgs), a.steps, a.warmup) for _ in range(a.rounds)]
+        res.setdefault("png_bytes", {})["level_%d" % level] = {f: os.path.getsize(os.path.join(t.image_dir, f))
+                                                               for f in sorted(os.listdir(t.image_dir))}
+    # what the grids add to training at the reference's interval: 5 steps with and without one display call behind them
+    # (wait=False, as train() calls it: the files of a call are awaited by the next one)
+    shape_trainer.PNG_COMPRESS_LEVEL = 1
+
+    def interval(display):
+        for _ in range(5):
+            t.train_step(batch)
+        if display:
+            t.save_img_results(batch, z, 5, name="average", imgs=imgs, wait=False)
+    res["five_steps_ms"] = {"without_display": [], "with_display": []}
+    for _ in range(a.rounds):                                # alternate
+        res["five_steps_ms"]["without_display"].append(wall(lambda: interval(False), a.steps, a.warmup))
+        res["five_steps_ms"]["with_display"].append(wall(lambda: interval(True), a.steps, a.warmup))
+    t.finish_images()
+    # the parts
+    nvis = 8
+    parts = {}
+    with torch.no_grad():
+        parts["generator_forward_nvis"] = wall(lambda: t.netG(z[:nvis], batch["bbox_maps_fwd"][:nvis], batch["bbox_maps_bwd"][:nvis],
+                                                              batch["bbox_fmaps"][:nvis]), a.steps, a.warmup)
+        parts["generator_forward_batch"] = wall(lambda: t.netG(z, batch["bbox_maps_fwd"], batch["bbox_maps_bwd"],
+                                                               batch["bbox_fmaps"]), a.steps, a.warmup)
+        fake = t.netG(z[:nvis], batch["bbox_maps_fwd"][:nvis], batch["bbox_maps_bwd"][:nvis], batch["bbox_fmaps"][:nvis])
+    caps = np.ones((nvis, 10), np.int64)
+    parts["caption_strip"] = wall(lambda: shape_utils.caption_strip(caps, ds.ixtoword, nvis, 64, 20, 12, 10, dev), a.steps, a.warmup)
+    strip = shape_utils.caption_strip(caps, ds.ixtoword, nvis, 64, 20, 12, 10, dev)
+    parts["one_grid_compose_and_copy"] = wall(lambda: shape_utils.build_super_images(
+        imgs[:nvis], caps, ds.ixtoword, fake, 64, font_max=20, font_size=12, max_word_num=10, strip=strip), a.steps, a.warmup)
+    grid = shape_utils.build_super_images(imgs[:nvis], caps, ds.ixtoword, fake, 64, font_max=20, font_size=12, max_word_num=10,
+                                          strip=strip)[0]
+    res["grid_shape"] = list(grid.shape)
+    for level in (6, 1, 0):
+        parts["one_png_encode_level_%d" % level] = wall(
+            lambda: Image.fromarray(grid).save(io.BytesIO(), format="PNG", compress_level=level), a.steps, a.warmup)
+    g = np.random.RandomState(0)
+    buf = io.BytesIO()
+    Image.fromarray(np.clip(np.cumsum(g.randn(480, 640, 3), 1) * 4 + 128, 0, 255).astype(np.uint8)).save(buf, format="JPEG", quality=90)
+    parts["decode_8_jpegs_640x480"] = wall(lambda: [load.get_imgs(buf.getvalue(), [64], branch_num=1) for _ in range(8)],
+                                           a.steps, a.warmup)
+    res["parts_ms"] = parts
+    # sampling: a synthetic split of whole batches, the trainer's own generator as the checkpoint
+    import time
+    ckpt = os.path.join(out_dir, "netG_epoch_0.pth")
+    torch.save({k: v.detach().cpu() for k, v in t.netG.state_dict().items()}, ckpt)
+    cfg.TRAIN.NET_G = ckpt
+    items = []
+    for k in range(a.sample_batches):
+        item = list(inputs(B, R, nbf, dev, seed=k)["item"])
+        item[9] = ["b%03d_%s" % (k, key) for key in item[9]]
+        items.append(tuple(item))
+    t.data_loader = items
+    t.sampling("test")                                       # warm-up pass (filter banks, allocator, directory)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    written, skipped = t.sampling("test")
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    res["sampling"] = {"images": written, "skipped": skipped, "seconds": dt, "images_per_s": written / dt}
+    cfg.TRAIN.NET_G = ""
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=40)
@@ -207,11 +337,13 @@ def main():
     ap.add_argument("--pcp", action="store_true")
     ap.add_argument("--vgg-weights", type=str, default="")
     ap.add_argument("--pcp-batches", type=str, default="40,16")
+    ap.add_argument("--display", action="store_true")
+    ap.add_argument("--sample-batches", type=int, default=10)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = torch.device("cuda:0")
-    if a.pcp:
-        line = json.dumps(pcp_main(a, dev))
+    if a.pcp or a.display:
+        line = json.dumps(display_main(a, dev) if a.display else pcp_main(a, dev))
         print(line)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
