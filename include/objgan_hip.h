@@ -16,7 +16,9 @@
  * becomes an explicit hipStream_t).  Everything else the reference step obtains from
  * cuDNN / cuBLAS / THC through PyTorch (conv, norms, attention bmm+softmax, masked max,
  * bilinear resize, Adam) is exported here with the same conventions so that the host side
- * (Python, ctypes) stays a thin binding.
+ * (Python, ctypes) stays a thin binding.  This file is compiled into every kernel source (csrc/common.h includes it) and
+ * read by the Python binding (objgan_hip/_lib.py derives its ctypes table from the declarations below), so a declaration
+ * is written here and nowhere else: `int` or `long` result, parameters that are pointers or int / long / float / double.
  *
  * Conventions (identical to the reference FFI, roi_align_cuda.c:7-40):
  *   - the library never allocates, frees or retains memory; the caller owns every buffer,

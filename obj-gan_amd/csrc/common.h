@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "objgan_hip.h"     // the C ABI: the compiler holds every definition against its declaration
 
 #define OG_WAVE 64
 

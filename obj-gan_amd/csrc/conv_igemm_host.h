@@ -170,8 +170,6 @@ static inline long og_phase_wmax_offset(int M, int Tg, int Cp) { return 4 * (((l
 // bf16 mode: floats the channel-blocked bf16 copy [N][Cp/16][H*W][16] of a source takes
 static inline long og_nhwc_bf16_floats(int N, int H, int W, int Cp) { return ((long)N * H * W * Cp / 2 + 3) & ~3L; }
 
-extern "C" long objgan_conv_packed_floats(int M, int C, int T);
-
 // conv_igemm_pack.hip
 int og_fill_pack(PackArgs& p, const float* w, float* wt, int N, int C, int H, int W, int Cout, int Cin, int Torig,
                  int transpose, int Tg, const int* src_tap, int PH, int PW, int act, int math, int* MT_out);

@@ -14,6 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 LIB_PATH = os.path.join(HERE, "libobjgan_hip.so")
 OBJ_DIR = os.path.join(CSRC, "build")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+HEADER = os.path.join(INCLUDE, "objgan_hip.h")      # the C ABI: csrc/common.h includes it, _lib.py reads it
 
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # OBJGAN_DEV=1: development build -- the OG_* switches of csrc/common.h (OG_KNOB) read the environment
@@ -60,8 +62,7 @@ def needs_build():
     except OSError:
         return True
     lib_m = os.path.getmtime(LIB_PATH)
-    for f in os.listdir(CSRC):
-        p = os.path.join(CSRC, f)
+    for p in [HEADER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC)]:
         if os.path.isfile(p) and os.path.getmtime(p) > lib_m:
             return True
     return False
@@ -96,11 +97,11 @@ def _build_locked(force, verbose):
         obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
         objs.append(obj)
         srcp = os.path.join(CSRC, src)
-        deps = [srcp] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+        deps = [srcp, HEADER] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
         if (not force and os.path.exists(obj)
                 and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in deps)):
             continue
-        cmd = [hipcc] + BASE_FLAGS + PER_FILE_FLAGS.get(src, []) + ["-c", srcp, "-o", obj]
+        cmd = [hipcc] + BASE_FLAGS + PER_FILE_FLAGS.get(src, []) + ["-I", INCLUDE, "-c", srcp, "-o", obj]
         if verbose:
             print("[objgan_hip.build]", " ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, cwd="/tmp" if os.path.isdir("/tmp") else None,

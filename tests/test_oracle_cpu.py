@@ -1,8 +1,10 @@
 """CPU tests (no GPU): the oracle is pinned against the reference and its golden vectors, the
 C-ABI library loads and exports every declared symbol, and the host-side logic behaves."""
+import ctypes
 import os
 import random
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -203,6 +205,67 @@ def test_c_abi_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.objgan_conv_packed_floats(388, 194, 9) == 512 * 208 * 9 * 3 // 2 + 1024   # 6-byte bf16x3 bank + |w| maxima
+    # the table is read from the header: nothing skipped, and restype is c_long exactly where the header says long
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+    in_code = set(re.findall(r"\b(objgan_[a-z0-9_]+)\s*\(", code))
+    assert len(_lib.parse_header(hdr)) == len(in_code) == len(table)
+    declared_long = set(re.findall(r"\blong\s+(objgan_[a-z0-9_]+)\s*\(", code))
+    assert declared_long and declared_long == set(_lib.LONG_RETURN)
+    for name in in_code:
+        want = ctypes.c_long if name in declared_long else ctypes.c_int
+        assert getattr(lib, name).restype is want, name
+
+
+def test_c_abi_header_parser_classifies_or_raises():
+    """parse_header on literal declarations: every pointer is c_void_p, the four scalars map to their ctypes, an empty
+    or void list is no argument -- and what it cannot classify raises instead of defaulting to a pointer"""
+    from objgan_hip import _lib
+    c = ctypes
+    got = _lib.parse_header("""
+        /* int objgan_in_a_comment(int a); */
+        // long objgan_in_a_line_comment(void);
+        int objgan_a(const unsigned char* p, const long* o, void* stream, long n, double b, float s, int k,
+                     float* const* grads);
+        long objgan_b();
+        long objgan_c(void);
+        int objgan_d(const int n, long);
+    """)
+    assert got == {"objgan_a": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_long, c.c_double, c.c_float, c.c_int,
+                                          c.c_void_p]),
+                   "objgan_b": (c.c_long, []), "objgan_c": (c.c_long, []),
+                   "objgan_d": (c.c_int, [c.c_int, c.c_long])}
+    for bad in ("int objgan_x(size_t n);", "int objgan_x(int a[4]);", "float objgan_x(int a);", "void objgan_x(int a);",
+                "unsigned long objgan_x(int a);", "int objgan_x(unsigned n);", "int objgan_x(int a, ...);",
+                "int objgan_x(int (*f)(int));", "int objgan_x(int a) { return a; }", "int objgan_x(int a, void);"):
+        with pytest.raises(_lib.ObjganHipError, match="objgan_x"):
+            _lib.parse_header("int objgan_ok(int a);\n" + bad)
+
+
+def test_kernel_sources_compile_against_the_header(tmp_path):
+    """csrc/common.h includes the header, so a definition that disagrees with its declaration does not compile: a copy
+    of the header with ONE long parameter narrowed to int, force-included ahead of pool.hip (which defines that entry
+    point), is a `conflicting types` error; the unaltered copy passes the same command (host pass, syntax only)."""
+    from objgan_hip import build
+    try:
+        hipcc = build._hipcc()
+    except RuntimeError:
+        pytest.skip("no hipcc")
+    hdr = open(build.HEADER).read()
+    decl = "int objgan_pool2d_forward(const float* x, float* y, int* idx, long planes,"
+    assert hdr.count(decl) == 1
+    good, bad = tmp_path / "good.h", tmp_path / "bad.h"
+    good.write_text(hdr)
+    bad.write_text(hdr.replace(decl, decl.replace("long planes", "int planes")))
+
+    def compile_with(header):
+        cmd = [hipcc] + build.BASE_FLAGS + ["-I", build.INCLUDE, "-include", str(header), "--offload-host-only",
+                                            "-fsyntax-only", os.path.join(build.CSRC, "pool.hip")]
+        return subprocess.run(cmd, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+    ok = compile_with(good)
+    assert ok.returncode == 0, ok.stdout
+    r = compile_with(bad)
+    assert r.returncode != 0 and "conflicting types for 'objgan_pool2d_forward'" in r.stdout, r.stdout
 
 
 def test_workspace_queries_are_host_only_and_consistent():
