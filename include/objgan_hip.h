@@ -439,6 +439,30 @@ long objgan_jpeg_plan(void* descs, int n, const long* file_offsets, const long* 
 int objgan_jpeg_decode(const unsigned char* files, const void* descs_host, const void* descs_dev, int n,
                        unsigned char* out, void* ws, long ws_bytes, const void* index_in, void* index_out, void* stream);
 
+/* ---- generated images: baseline JPEG encode on the device (csrc/jpeg_enc.hip) -------------------------------------
+ * Replaces the per-image host loop of reference image_generation/evaluator.py:225-233 (save_singleimages: four fp32
+ * elementwise ops, .byte(), .cpu(), Image.fromarray(...).save('<key>_<sent>.jpg')): a batch of n RGB images of one size,
+ * H and W multiples of 16, -> the files Pillow's default save writes (JFIF 1.1, YCbCr 4:2:0, the Annex-K Huffman tables,
+ * one interleaved scan), BYTE FOR BYTE; integer arithmetic throughout (jccolor.c, jcsample.c h2v2, jfdctint.c, jcdctmgr.c,
+ * jchuff.c).  Nothing is encoded approximately: what the device does not encode is refused before any launch.
+ *
+ * objgan_jpeg_enc_header  HOST ONLY.  The objgan_jpeg_enc_header_bytes() = 623 bytes in front of the entropy-coded data
+ *                         for (H, W, quality 1..100: jpeg_quality_scaling, force_baseline).  The kernels read the
+ *                         quantisation and Huffman tables from a device copy of it.
+ * objgan_jpeg_enc_plan    HOST ONLY.  -> workspace bytes, *slot_bytes = bytes per image in the output buffer (the worst
+ *                         case the code tables allow; derivation in the source); or -reason for what is refused: 1 empty
+ *                         batch, 2 H or W no multiple of 16, 3 a side over 4096, 4 quality outside 1..100, 5 form.
+ * objgan_jpeg_encode      images: form 0 uint8 [n][H][W][3], form 1 fp32 [n][3][H][W] in [-1, 1] (bytes as the host loop
+ *                         makes them: add 1, div 2, mul 255, clamp, truncate, one fp32 rounding each).  out: image i's file
+ *                         at out + i * slot_bytes, lengths[i] its byte count (-1: it did not fit its slot -- cannot happen
+ *                         with the plan's slot size, and is bounds-checked all the same).  stages: 1 transform
+ *                         (-> int16 zigzag coefficients in ws), 2 entropy coding, 3 both.  Asynchronous on `stream`. */
+long objgan_jpeg_enc_header_bytes(void);
+int objgan_jpeg_enc_header(int H, int W, int quality, unsigned char* out);
+long objgan_jpeg_enc_plan(int n, int H, int W, int quality, int form, long* slot_bytes);
+int objgan_jpeg_encode(const void* images, int form, int n, int H, int W, const unsigned char* header_dev, unsigned char* out,
+                       long slot_bytes, int* lengths, void* ws, long ws_bytes, int stages, void* stream);
+
 /* ---- per-box instance masks on the device (the loader side of the path) --------------------
  * Replaces the four `skimage.transform.resize(mask, [s, s])` calls per box of reference
  * image_generation/miscc/load.py:160-176 (s = 32, 64, 128, 256 from the 64 x 64 instance mask): `count` square

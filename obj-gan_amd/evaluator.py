@@ -308,10 +308,19 @@ class condGANEvaluator(object):
         Image.fromarray(img_set).save(path)
         return path
 
-    def save_singleimages(self, images, keys, sent_ids):
-        """evaluator.py:225-233: [-1, 1] images -> <Image>/<key>_<sent id>.jpg"""
+    def save_singleimages(self, images, keys, sent_ids, device_jpeg=True):
+        """evaluator.py:225-233: [-1, 1] images -> <Image>/<key>_<sent id>.jpg.  A batch on the device whose sides are
+        multiples of 16 is encoded there (ops.jpeg_encode: the same bytes Pillow writes, one launch pair and two copies per
+        batch); everything else -- a CPU tensor, an odd size, device_jpeg=False -- takes the reference's host loop."""
         from PIL import Image
         images = images.detach()
+        if device_jpeg and images.is_cuda:
+            from objgan_hip import ops
+            if ops.jpeg_encode_refusal(images) == 0:
+                for i, data in enumerate(ops.jpeg_encode(images)):
+                    with open('%s/%s_%d.jpg' % (self.image_dir, keys[i], sent_ids[i]), 'wb') as f:
+                        f.write(data)
+                return
         for i in range(images.size(0)):
             img = images[i].add(1).div(2).mul(255).clamp(0, 255).byte()
             ndarr = img.permute(1, 2, 0).cpu().numpy()

@@ -1806,6 +1806,91 @@ def jpeg_decode(files, device, cache=None, keys=None):
     return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, h, w in zip(offs, hs, ws)]
 
 
+# ---- generated images: baseline JPEG encode on the device (csrc/jpeg_enc.hip) ----------------------------
+class JpegEncodeRefused(_lib.ObjganHipError):
+    """the batch is not what the device encodes (one size with sides that are multiples of 16, uint8 [n, H, W, 3] or fp32
+    [n, 3, H, W], quality 1..100): the caller takes the host route knowingly -- nothing is encoded approximately"""
+
+    REASONS = {1: "empty batch", 2: "height and width must be multiples of 16 (and at least 16)", 3: "a side is over 4096",
+               4: "quality must be an integer in 1..100",
+               5: "images must be uint8 [n, H, W, 3] or float32 [n, 3, H, W] (RGB; no grey, no other sampling or options)"}
+
+    def __init__(self, reason):
+        super().__init__("jpeg_encode: %s" % self.REASONS.get(reason, "reason %d" % reason))
+        self.reason = reason
+
+
+def _jpeg_enc_plan(images, quality):
+    """HOST ONLY (no GPU call) -> (reason, form, n, H, W, slot bytes, workspace bytes); reason 0: the device encodes it"""
+    form = -1
+    if torch.is_tensor(images) and images.dim() == 4:
+        if images.dtype == torch.uint8 and images.shape[3] == 3:
+            form, (n, H, W) = 0, images.shape[:3]
+        elif images.dtype == torch.float32 and images.shape[1] == 3:
+            form, n, (H, W) = 1, images.shape[0], images.shape[2:]
+    if form < 0:
+        return 5, form, 0, 0, 0, 0, 0
+    if isinstance(quality, bool) or not isinstance(quality, int):
+        return 4, form, 0, 0, 0, 0, 0
+    slot = ctypes.c_long(0)
+    ws = int(_lib.load().objgan_jpeg_enc_plan(int(n), int(H), int(W), quality, form, ctypes.byref(slot)))
+    return (-ws if ws <= 0 else 0), form, int(n), int(H), int(W), int(slot.value), ws
+
+
+def jpeg_encode_refusal(images, quality=75):
+    """HOST ONLY: 0 if jpeg_encode takes this batch, else the JpegEncodeRefused reason"""
+    return _jpeg_enc_plan(images, quality)[0]
+
+
+_JPEG_ENC_HEADERS = {}
+
+
+def _jpeg_enc_header(H, W, quality, device):
+    """the 623 bytes in front of every stream of this (H, W, quality), built once on the host, kept on the device"""
+    key = (H, W, quality, str(device))
+    if key not in _JPEG_ENC_HEADERS:
+        lib = _lib.load()
+        buf = (ctypes.c_ubyte * int(lib.objgan_jpeg_enc_header_bytes()))()
+        _lib.call("objgan_jpeg_enc_header", H, W, quality, buf)
+        _JPEG_ENC_HEADERS[key] = torch.frombuffer(bytearray(buf), dtype=torch.uint8).to(device)
+    return _JPEG_ENC_HEADERS[key]
+
+
+def jpeg_encode_device(images, quality=75, stages=3, state=None):
+    """The launches of jpeg_encode without its copies: -> (out uint8 [n, slot], lengths int32 [n], state); `stages` 1 / 2
+    with the `state` of the call before runs the transform and the entropy stage apart (tools/jpeg_encode_time.py)."""
+    reason, form, n, H, W, slot, ws_bytes = _jpeg_enc_plan(images, quality)
+    if reason:
+        raise JpegEncodeRefused(reason)
+    if images.device.type != "cuda":
+        raise _lib.ObjganHipError("jpeg_encode: needs a HIP device (no CPU path)")
+    images = images.detach().contiguous()
+    device = images.device
+    if state is None:
+        state = (torch.empty((n, slot), dtype=torch.uint8, device=device), torch.empty(n, dtype=torch.int32, device=device),
+                 torch.empty((ws_bytes + 15) // 16 * 16, dtype=torch.uint8, device=device))
+    out, lengths, work = state
+    _lib.call("objgan_jpeg_encode", _p(images), form, n, H, W, _p(_jpeg_enc_header(H, W, quality, device)), _p(out), slot,
+              _p(lengths), _p(work), work.numel(), stages, _stream())
+    return out, lengths, state
+
+
+def jpeg_encode(images, quality=75):
+    """images: a batch on the device, uint8 [n, H, W, 3] or fp32 [n, 3, H, W] in [-1, 1] (the generator's output; bytes as
+    add(1).div(2).mul(255).clamp(0, 255).byte() makes them), H and W multiples of 16 -> list of n `bytes`: the files
+    PIL.Image.fromarray(img).save(path, format='JPEG', quality=quality) writes, byte for byte (reference evaluator.py:225-233).
+    Two device-to-host copies whatever n: the lengths, then the used bytes.  Raises JpegEncodeRefused for anything else."""
+    out, lengths, _ = jpeg_encode_device(images, quality)
+    lens = lengths.cpu().tolist()
+    if min(lens) < 0:
+        raise _lib.ObjganHipError("jpeg_encode: image %d did not fit its slot" % lens.index(min(lens)))
+    packed = torch.cat([out[i, :ln] for i, ln in enumerate(lens)]).cpu().numpy().tobytes()
+    ends = [0]
+    for ln in lens:
+        ends.append(ends[-1] + ln)
+    return [packed[a:b] for a, b in zip(ends[:-1], ends[1:])]
+
+
 # ---- training images: Pillow's antialiased bilinear resize + ToTensor + Normalize on the device -------
 def resize_pil_bilinear_device(src, offs, hs, ws, sizes):
     """resize_pil_bilinear on images that are ALREADY on the device (jpeg_decode_batch's hand-over): src uint8 buffer, image b
