@@ -474,6 +474,32 @@ int objgan_jpeg_encode(const void* images, int form, int n, int H, int W, const 
 int objgan_mask_resize(const double* src, int count, int n, int nsizes, const int* sizes, double* const* out,
                        const int* ntaps, const double* taps, void* stream);
 
+/* ---- instance masks from COCO polygons (csrc/coco_masks.hip) ------------------------------------------------
+ * The mask step of the reference's annotation preprocessing (image_generation/miscc/load.py:608-622,
+ * shape_generation/datasets.py:347-361): per instance `COCO.segToMask(rings, H, W)` (skimage.draw.polygon per ring,
+ * OR-ed) -> astype(float) -> skimage.transform.resize(mask, [S, S]).  One call takes a batch of A instances of
+ * different image sizes and returns out[A][S][S] float64, bit for bit what obj-gan_amd/miscc/coco_prep.py computes on
+ * the host with numpy + scipy.ndimage (even-odd crossing rule of skimage's point_in_polygon in float64 at integer pixel
+ * coordinates; per-axis Gaussian, axis 0 then axis 1, mode mirror; order-1 zoom with grid_mode, mode mirror; clip to
+ * the rasterised mask's own minimum and maximum).  The full-size mask exists only as a bit plane in the workspace, and
+ * the filter is evaluated only at the <= 2 S rows and columns the zoom reads.
+ *   verts      [nverts][2] float64 (x, y), already clipped by the caller; ring r is verts[ring_off[r] .. ring_off[r + 1])
+ *   ring_off   [nrings + 1], inst_ring [A + 1]: instance a owns rings inst_ring[a] .. inst_ring[a + 1] (none: empty mask)
+ *   hs, ws     [A] image height and width, 1 .. Hmax / Wmax
+ *   taps       float64 table of normalised Gaussian weights (computed by the caller as scipy computes them);
+ *   tap_off    [A][2][2] = per instance and axis {first index in taps, count}; count = 2 radius + 1, or 0: no filter on
+ *              that axis (it does not shrink)
+ * All arrays are device memory.  An instance whose table entries contradict the scalar arguments is answered with NaN.
+ * objgan_poly_masks_covers  HOST ONLY.  1 when the kernels cover an instance of this size: S <= 64, sides <= 1024, tap
+ *                           counts <= 65 (radius 32; COCO's 640 -> 64 has radius 18).  What is not covered is refused
+ *                           by objgan_poly_masks (returns 0) and is left to the caller's host route.
+ * objgan_poly_masks_plan    HOST ONLY.  -> workspace bytes for a batch (0: refused). */
+int objgan_poly_masks_covers(int H, int W, int S, int ntaps0, int ntaps1);
+long objgan_poly_masks_plan(int A, int Hmax, int Wmax);
+int objgan_poly_masks(const double* verts, long nverts, const int* ring_off, const int* inst_ring, int nrings,
+                      const int* hs, const int* ws, int A, int Hmax, int Wmax, int S, const double* taps,
+                      const int* tap_off, int ntaps_total, double* out, void* ws_buf, long ws_bytes, void* stream);
+
 /* ---- evaluation statistics on the device (csrc/eval_stats.hip) -------------------------------------------
  * objgan_bilinear_halfpixel_forward  the input preparation of the FID feature network (reference
  *     image_generation/model.py:433-441): y[N, C, OH, OW] = F.interpolate(x, (OH, OW), 'bilinear',

@@ -17,9 +17,12 @@ training path reads:
   <data_dir>/gen_masks/<key>/<i>/boxes.txt  layouts of the box generator (sample.py), "x,y,w,h,label,0" per line;
                                       <split>_gen_insanns.pickle is built from them when it is missing
 
-Building those files from raw COCO (captions via nltk / spacy / torchtext, masks via
-pycocotools) is preprocessing, not the training path: where a prepared file is missing the
-readers below raise instead of trying.  Third-party arithmetic the reference delegates to
+  <data_dir>/insanns/instances_<train|val>2014.json  COCO's instance annotations: <split>_gt_insanns.pickle is built
+                                      from them when it is missing (miscc/coco_prep.py, prepare_data.py)
+
+Building the caption files from raw COCO (nltk / spacy / torchtext) is preprocessing, not the
+training path: where one of them is missing the readers below raise instead of trying.
+Third-party arithmetic the reference delegates to
 packages that are absent here is restated and named where it happens (PIL bilinear resize for
 torchvision.transforms.Resize, scipy.ndimage for skimage.transform.resize): parity of those two
 is against the restatement, not against the packages (LAB.md section 6, "data path").
@@ -222,8 +225,19 @@ def load_anns_data(data_dir, split, postfix, ann_type, filenames, imsize, fmsize
                 pickle.dump([insanns_dict], f, protocol=2)
             print('Save to: ', filepath)
             return insanns_dict
-        raise FileNotFoundError("%s: build it with the reference's preprocessing (pycocotools)%s" % (
-            filepath, ", or run sample.py to write <data_dir>/gen_masks/" if ann_type == 'gen' else ""))
+        if ann_type == 'gt':
+            from miscc import coco_prep
+            if os.path.isfile(coco_prep.annotation_file(data_dir, split)):
+                # COCO's own instance JSON: build the pickle as the reference does (masks on the GPU when there is one)
+                insanns_dict = coco_prep.build_gt_insanns(data_dir, filenames, split, imsize, fmsize, cats_index_dict,
+                                                          device=coco_prep.default_device())
+                with open(filepath, 'wb') as f:
+                    pickle.dump([insanns_dict], f, protocol=2)
+                print('Save to: ', filepath)
+                return insanns_dict
+        raise FileNotFoundError("%s: %s" % (filepath, (
+            "run sample.py to write <data_dir>/gen_masks/" if ann_type == 'gen' else
+            "put COCO's instances_<train|val>2014.json under <data_dir>/insanns/ (prepare_data.py builds the pickle from it)")))
     return _load_pickle(filepath, encoding='latin1')[0]
 
 

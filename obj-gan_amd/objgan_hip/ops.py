@@ -1999,6 +1999,74 @@ def resize_masks(masks, sizes):
     return outs
 
 
+# ---- instance masks from COCO polygons (csrc/coco_masks.hip) --------------------------------------------
+def _poly_taps(n, other, S):
+    """weights of skimage.transform.resize's anti-aliasing filter along an axis of n samples going to S (the other axis
+    has `other`), or None where scipy.ndimage.gaussian_filter skips the axis: nothing shrinks, or sigma is 0"""
+    if max(n / float(S), other / float(S)) <= 1:
+        return None
+    sigma = max(0.0, (n / float(S) - 1) / 2.0)
+    return _gaussian_taps(sigma) if sigma > 1e-15 else None
+
+
+def poly_masks_covers(H, W, S):
+    """whether csrc/coco_masks.hip takes an H x W instance resized to S x S (sides <= 1024, filter radius <= 32, S <= 64);
+    what it does not take is the caller's to route to the host (miscc/coco_prep.py)"""
+    t0, t1 = _poly_taps(H, W, S), _poly_taps(W, H, S)
+    return bool(_q("objgan_poly_masks_covers", int(H), int(W), int(S), 0 if t0 is None else len(t0),
+                   0 if t1 is None else len(t1)))
+
+
+def poly_masks(verts, ring_off, inst_ring, hs, ws, S, device):
+    """A batch of A polygon instances of different image sizes -> float64 [A, S, S] on `device`: each rasterised at its
+    hs[a] x ws[a] (`COCO.segToMask`: skimage's even-odd rule per ring, rings OR-ed) and resized with
+    skimage.transform.resize's defaults as scipy evaluates them, bit for bit `miscc.coco_prep`'s host route.
+    Host arrays in: verts float64 [nverts, 2] (x, y; clipped by the caller), ring r = verts[ring_off[r]:ring_off[r + 1]],
+    instance a owns rings inst_ring[a] .. inst_ring[a + 1].  Every instance must pass `poly_masks_covers`."""
+    import numpy as np
+    verts = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 2)
+    ring_off = np.ascontiguousarray(ring_off, dtype=np.int32)
+    inst_ring = np.ascontiguousarray(inst_ring, dtype=np.int32)
+    hs, ws = np.ascontiguousarray(hs, dtype=np.int32), np.ascontiguousarray(ws, dtype=np.int32)
+    A, S = len(hs), int(S)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ObjganHipError("poly_masks runs on the MI355X only (got %s); the host route is miscc.coco_prep" % device)
+    out = torch.empty((A, S, S), dtype=torch.float64, device=device)
+    if A == 0:
+        return out
+    nrings = len(ring_off) - 1
+    if (len(ws) != A or len(inst_ring) != A + 1 or nrings < 0 or ring_off[0] != 0 or ring_off[-1] != len(verts)
+            or np.any(np.diff(ring_off) < 0) or inst_ring[0] != 0 or inst_ring[-1] != nrings or np.any(np.diff(inst_ring) < 0)):
+        raise _lib.ObjganHipError("poly_masks: ring_off / inst_ring do not partition the vertices and rings")
+    table, tap_off, seen = [], np.zeros((A, 2, 2), np.int32), {}
+    for a in range(A):
+        H, W = int(hs[a]), int(ws[a])
+        if not poly_masks_covers(H, W, S):
+            raise _lib.ObjganHipError("poly_masks: a %d x %d instance to %d x %d is outside the kernel's caps" % (H, W, S, S))
+        for axis, (n, other) in enumerate(((H, W), (W, H))):
+            if (n, other) not in seen:
+                w = _poly_taps(n, other, S)
+                seen[(n, other)] = (0, 0) if w is None else (sum(len(t) for t in table), len(w))
+                if w is not None:
+                    table.append(w)
+            tap_off[a, axis] = seen[(n, other)]
+    taps = np.concatenate(table) if table else np.zeros((0,))
+    Hmax, Wmax = int(hs.max()), int(ws.max())
+    ws_bytes = int(_q("objgan_poly_masks_plan", A, Hmax, Wmax))
+    if ws_bytes <= 0:
+        raise _lib.ObjganHipError("poly_masks: a batch of %d instances up to %d x %d is refused" % (A, Hmax, Wmax))
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+
+    def up(x):
+        return torch.from_numpy(x).to(device)
+    d = [up(x) for x in (verts, ring_off, inst_ring, hs, ws, taps, tap_off)]
+    with torch.cuda.device(device):
+        _lib.call("objgan_poly_masks", _p(d[0]), len(verts), _p(d[1]), _p(d[2]), nrings, _p(d[3]), _p(d[4]), A, Hmax, Wmax,
+                  S, _p(d[5]), _p(d[6]), len(taps), _p(out), _p(work), ws_bytes, _stream())
+    return out
+
+
 # ---- caption / attention snapshot grids (csrc/snapshot.hip) ---------------------------------------------
 _EXPAND = {}
 

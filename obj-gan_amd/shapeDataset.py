@@ -2,8 +2,9 @@
 
 Reads what the reference's preparation left in the data directory -- `<split>_shape_insanns.pickle` (per image: rois,
 fm_rois, instance masks, pooled mask, box maps at 64x64 and 16x16, num_rois), `<split>/filenames.pickle`,
-`captions.pickle` (for the word index of the category names) and `categories.txt` -- and never builds them: making the
-annotation pickle from the COCO json needs pycocotools and skimage and stays an offline step.
+`captions.pickle` (for the word index of the category names) and `categories.txt`.  The annotation pickle is built
+from `<data_dir>/insanns/instances_<train|val>2014.json` when it is missing (miscc/coco_prep.py: the reference's
+`load_insanns` without pycocotools and skimage, masks on the GPU when there is one); the others are only read.
 
 An item is the reference's minus the image (only its display path reads it: `images_for` fetches the images of a
 batch's keys from `<split>_imgs.bigfile` when a grid is drawn), and with the box maps in their compact
@@ -92,7 +93,8 @@ class TextDataset(data.Dataset):
         self.n_words = len(self.ixtoword)
         self.class_id = self.load_class_id(os.path.join(data_dir, split), len(self.filenames))
         self.cats_dict, self.cats_index_dict = self.load_cats()
-        self.insanns_dict = self.load_anns_data(data_dir, split)
+        self.insanns_dict = self.load_anns_data(data_dir, split, self.filenames, self.imsize, self.fmsize,
+                                                self.cats_index_dict)
         self._img_bytes = self._img_index = None
 
     @staticmethod
@@ -132,11 +134,19 @@ class TextDataset(data.Dataset):
         return cats_dict, cats_index_dict
 
     @staticmethod
-    def load_anns_data(data_dir, split):
+    def load_anns_data(data_dir, split, filenames=None, imsize=None, fmsize=None, cats_index_dict=None):
         path = os.path.join(data_dir, '%s_shape_insanns.pickle' % split)
         if not os.path.isfile(path):
-            raise IOError("%s not found: the instance-annotation pickle is made offline by the reference's "
-                          "shape_generation/datasets.py (pycocotools + skimage) and only read here" % path)
+            from miscc import coco_prep
+            if filenames is None or not os.path.isfile(coco_prep.annotation_file(data_dir, split)):
+                raise IOError("%s not found, and no %s to build it from (prepare_data.py)"
+                              % (path, coco_prep.annotation_file(data_dir, split)))
+            insanns_dict = coco_prep.build_shape_insanns(data_dir, filenames, split, imsize, fmsize, cats_index_dict,
+                                                         device=coco_prep.default_device())
+            with open(path, 'wb') as f:
+                pickle.dump([insanns_dict], f, protocol=2)
+            print('Save to: ', path)
+            return insanns_dict
         with open(path, 'rb') as f:
             return pickle.load(f)[0]
 
