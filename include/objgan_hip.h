@@ -220,6 +220,28 @@ int objgan_lstm_bidir_forward_state(const float* table, const long* captions, co
                                     float* out, float* hn, float* cn, int B, int L, int Lout, int I, int H,
                                     int ntoken, void* stream);
 
+/* ---- trainable text encoder (csrc/lstm_train.hip; DAMSM pretraining).  Same tensors and limits as the frozen pass.
+ * keep (nullable) [B][L][I] uint8 is the embedding dropout's keep-mask and scale = 1 / (1 - p): the embedded word is
+ * multiplied by keep * scale before the gate sums.  With keep = NULL, out and hn are bit for bit those of
+ * objgan_lstm_bidir_forward.  ws: objgan_lstm_bidir_train_ws_floats(B, L, I, H) floats (host-only query), sections in
+ * this order: gates [B][2][L][4H] (activated i, f, g, o), cell [B][2][L][H], hidden [B][2][L][H], x [B][L][I] (the
+ * words after dropout) -- written by the forward pass -- then dgate [B][2][L][4H] (gate pre-activation deltas) and
+ * dx [B][L][I], written by the backward pass of the same step; all zero at positions past a caption's length.
+ * backward: d_out [B][2H][Lout] and d_hn [B][2H] (either may be NULL: zero); w_ih [2][4H][I] and w_hh [2][4H][H] are
+ *     the UNTRANSPOSED weight_ih_l0(_reverse) / weight_hh_l0(_reverse).  Gradients in the same layouts: d_w_ih
+ *     [2][4H][I], d_w_hh [2][4H][H], d_b_ih == d_b_hh [2][4H], d_table [ntoken][I] (rows of tokens not in the batch are
+ *     zero).  Every element is written; no float atomics, bit-reproducible. */
+long objgan_lstm_bidir_train_ws_floats(int B, int L, int I, int H);
+int objgan_lstm_bidir_train_forward(const float* table, const long* captions, const int* lens,
+                                    const unsigned char* keep, float scale,
+                                    const float* wt_ih, const float* wt_hh, const float* b_ih, const float* b_hh,
+                                    float* out, float* hn, float* ws, long ws_floats,
+                                    int B, int L, int Lout, int I, int H, int ntoken, void* stream);
+int objgan_lstm_bidir_backward(const float* d_out, const float* d_hn, const long* captions, const int* lens,
+                               const unsigned char* keep, float scale, const float* w_ih, const float* w_hh,
+                               float* ws, long ws_floats, float* d_w_ih, float* d_w_hh, float* d_b_ih, float* d_b_hh,
+                               float* d_table, int B, int L, int Lout, int I, int H, int ntoken, void* stream);
+
 /* ---- box generator, sampling path (reference box_generation DecoderRNN.forward_step, is_training=0): one launch
  * decodes B captions from the encoder's (h_n, c_n) to label / box sequences of <= T steps.  h0, c0 [B][H];
  * noise [B][T][6] doubles (uniform, normal, normal for the xy draw, then for the wh draw).  l_emb [L][H]; xy_w, wh_w,

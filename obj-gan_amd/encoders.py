@@ -256,9 +256,18 @@ class CNN_ENCODER(nn.Module):
         self.emb_cnn_code = nn.Linear(2048, nef)
         self.emb_features.weight.data.uniform_(-0.1, 0.1)
         self.emb_cnn_code.weight.data.uniform_(-0.1, 0.1)
+        # Set by the DAMSM pretraining loop (damsm_trainer.py).  requires_grad alone cannot be the switch: a freshly
+        # built encoder has it on, and the generator's DAMSM term differentiates such an encoder down to the image.
+        self.train_projections = False
 
     def forward(self, x):
         x = ops.bilinear_resize(x, 299, 299)
+        if self.train_projections and self.emb_features.weight.requires_grad:
+            # DAMSM pretraining: the two projections learn; the trunk stays frozen and the image is data (no gradient)
+            with torch.no_grad():
+                regions, code = inception_trunk(self, x, want_regions=True)
+            return (ops.conv2d(regions, self.emb_features.weight),
+                    ops.linear(code, self.emb_cnn_code.weight, self.emb_cnn_code.bias))
         regions, code = inception_trunk(self, x, want_regions=True)
         return (ops.conv2d_frozen(regions, self.emb_features.weight.detach()),
                 ops.linear(code, self.emb_cnn_code.weight.detach(), self.emb_cnn_code.bias.detach()))

@@ -200,8 +200,9 @@ class RNN_ENCODER(nn.Module):
     state-dict keys (`encoder.weight`, `rnn.weight_ih_l0`, `rnn.weight_hh_l0_reverse`, ...) and
     `forward(captions, cap_lens, max_len) -> (words_emb [B, nhidden, max_len], sent_emb [B, nhidden])`.
     nn.Embedding / nn.LSTM are parameter holders; the forward pass is one fused kernel per step
-    (objgan_lstm_bidir_forward).  The encoder is frozen on this path (trainer.py:97-100 of the
-    reference): forward only, eval-mode dropout (identity)."""
+    (objgan_lstm_bidir_forward).  The encoder is frozen on the generator's path (trainer.py:97-100 of the
+    reference): in eval mode forward only, dropout the identity.  In training mode (DAMSM pretraining) the pass is
+    ops.lstm_bidir_train: the same values with the embedding dropout applied, and gradients to every parameter."""
 
     def __init__(self, ntoken, ninput=300, drop_prob=0.5, nhidden=128, nlayers=1, bidirectional=True):
         super(RNN_ENCODER, self).__init__()
@@ -222,6 +223,8 @@ class RNN_ENCODER(nn.Module):
                            dropout=self.drop_prob, bidirectional=self.bidirectional)
         self.encoder.weight.data.uniform_(-0.1, 0.1)
         self._packed = None
+        self.fixed_keep_mask = None         # injects the dropout mask for parity tests, as CA_NET.fixed_eps does
+        self.generator = None
 
     def init_hidden(self, bsz):
         w = next(self.parameters()).data
@@ -244,9 +247,26 @@ class RNN_ENCODER(nn.Module):
             self._packed = (key, wt_ih, wt_hh, b_ih, b_hh)
         return self._packed[1:]
 
+    def _keep_mask(self, captions):
+        """the embedding dropout's keep-mask, uint8 [B, L, ninput]: `fixed_keep_mask` when set, else drawn on the device
+        (torch.rand with `self.generator`, a torch.Generator of the captions' device, or the default stream)"""
+        if self.fixed_keep_mask is not None:
+            return self.fixed_keep_mask
+        if self.drop_prob <= 0:
+            return None
+        u = torch.rand(tuple(captions.shape) + (self.ninput,), device=captions.device, generator=self.generator)
+        return (u >= self.drop_prob).to(torch.uint8)
+
     def forward(self, captions, cap_lens, max_len, mask=None):
-        if self.training and self.drop_prob > 0:
-            raise NotImplementedError("RNN_ENCODER is frozen on the training path: call .eval()")
+        if self.training:
+            # DAMSM pretraining: the same pass with gradients to the table and the eight LSTM tensors.  nn.LSTM's own
+            # dropout acts between layers only -- none for one layer -- so the embedding dropout is all there is.
+            self._packed = None             # the optimiser writes the weights through raw pointers
+            r = self.rnn
+            return ops.lstm_bidir_train(self.encoder.weight, captions, cap_lens,
+                                        (r.weight_ih_l0, r.weight_ih_l0_reverse), (r.weight_hh_l0, r.weight_hh_l0_reverse),
+                                        (r.bias_ih_l0, r.bias_ih_l0_reverse), (r.bias_hh_l0, r.bias_hh_l0_reverse),
+                                        max_len, self._keep_mask(captions), self.drop_prob)
         wt_ih, wt_hh, b_ih, b_hh = self._weights()
         words_emb, sent_emb = ops.lstm_bidir_forward(self.encoder.weight.detach(), captions, cap_lens,
                                                      wt_ih, wt_hh, b_ih, b_hh, max_len)

@@ -32,10 +32,13 @@ if os.environ.get("OBJGAN_DEV") == "1":
 # The layout stage restates numpy's fp64 post-processing operation by operation; its one fma is written out.
 # The JPEG encoder's fp32 input form rounds (x + 1) / 2 * 255 operation by operation, like the host loop it replaces.
 # The COCO instance masks restate skimage's crossing rule and scipy.ndimage's filter and zoom in float64, operation by operation.
+# The trainable text encoder repeats the frozen pass's fmaf chains explicitly (bit-identical forward) and rounds its
+# backward products one by one.
 PER_FILE_FLAGS = {"roi_align.hip": ["-ffp-contract=off", "-munsafe-fp-atomics"], "resize_pil.hip": ["-ffp-contract=off"],
                   "snapshot.hip": ["-ffp-contract=off"], "box_decode.hip": ["-ffp-contract=off"],
                   "box_train.hip": ["-ffp-contract=off"], "layout.hip": ["-ffp-contract=off"],
-                  "jpeg_enc.hip": ["-ffp-contract=off"], "coco_masks.hip": ["-ffp-contract=off"]}
+                  "jpeg_enc.hip": ["-ffp-contract=off"], "coco_masks.hip": ["-ffp-contract=off"],
+                  "lstm_train.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -2353,6 +2353,116 @@ def lstm_bidir_forward(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, max_len,
 
 
 # ----------------------------------------------------------------------------------------------
+# trainable text encoder (DAMSM pretraining; csrc/lstm_train.hip)
+# ----------------------------------------------------------------------------------------------
+def lstm_train_ws_sections(B, L, I, H):
+    """-> ({name: (offset, shape)}, total floats) of the workspace objgan_lstm_bidir_train_forward / _backward share
+    (include/objgan_hip.h); the total is the library's own answer and the sections must add up to it."""
+    shapes = (("gates", (B, 2, L, 4 * H)), ("cell", (B, 2, L, H)), ("hidden", (B, 2, L, H)), ("x", (B, L, I)),
+              ("dgate", (B, 2, L, 4 * H)), ("dx", (B, L, I)))
+    sections, off = {}, 0
+    for name, shape in shapes:
+        sections[name] = (off, shape)
+        off += math.prod(shape)
+    total = int(_lib.load().objgan_lstm_bidir_train_ws_floats(B, L, I, H))
+    if total != off:
+        raise _lib.ObjganHipError("lstm_train: workspace of %d floats, sections add up to %d" % (total, off))
+    return sections, total
+
+
+def lstm_train_ws_view(ws, name, B, L, I, H):
+    off, shape = lstm_train_ws_sections(B, L, I, H)[0][name]
+    return ws[off:off + math.prod(shape)].view(shape)
+
+
+def _lstm_train_args(captions, lens, keep_mask, I):
+    if not captions.is_cuda or captions.dtype != torch.int64:
+        raise _lib.ObjganHipError("lstm: captions must be an int64 tensor on the GPU")
+    captions = _c(captions)
+    lens = _c(lens.to(device=captions.device, dtype=torch.int32))
+    if keep_mask is not None:
+        if (not keep_mask.is_cuda or keep_mask.dtype != torch.uint8
+                or tuple(keep_mask.shape) != tuple(captions.shape) + (I,)):
+            raise _lib.ObjganHipError("lstm_train: keep_mask is a uint8 [B, L, I] tensor on the GPU")
+        keep_mask = _c(keep_mask)
+    return captions, lens, keep_mask
+
+
+def lstm_bidir_train_forward(table, captions, lens, wt_ih, wt_hh, b_ih, b_hh, max_len, keep_mask=None, scale=1.0,
+                             ws=None):
+    """raw objgan_lstm_bidir_train_forward over the packed [2][I][4H] / [2][H][4H] / [2][4H] weights of
+    lstm_bidir_forward -> (words_emb, sent_emb, ws)"""
+    _chk(table, wt_ih, wt_hh, b_ih, b_hh, ws)
+    B, L = captions.shape
+    I, G = wt_ih.shape[1], wt_ih.shape[2]
+    H = G // 4
+    captions, lens, keep_mask = _lstm_train_args(captions, lens, keep_mask, I)
+    n = int(_lib.load().objgan_lstm_bidir_train_ws_floats(B, L, I, H))
+    if ws is None:
+        ws = torch.empty(n, dtype=_F32, device=captions.device)
+    out = torch.empty((B, 2 * H, int(max_len)), dtype=_F32, device=captions.device)
+    hn = torch.empty((B, 2 * H), dtype=_F32, device=captions.device)
+    _lib.call("objgan_lstm_bidir_train_forward", _p(table), _p(captions), _p(lens), _p(keep_mask), float(scale),
+              _p(wt_ih), _p(wt_hh), _p(b_ih), _p(b_hh), _p(out), _p(hn), _p(ws), ws.numel(), B, L, int(max_len), I, H,
+              table.shape[0], _stream())
+    return out, hn, ws
+
+
+def lstm_bidir_backward(d_out, d_hn, captions, lens, w_ih, w_hh, ws, ntoken, max_len, keep_mask=None, scale=1.0):
+    """raw objgan_lstm_bidir_backward over the stacked UNTRANSPOSED weights w_ih [2][4H][I], w_hh [2][4H][H] and the
+    workspace the forward pass left -> (d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_table), freshly allocated"""
+    _chk(d_out, d_hn, w_ih, w_hh, ws)
+    B, L = captions.shape
+    G, I = w_ih.shape[1], w_ih.shape[2]
+    H = G // 4
+    captions, lens, keep_mask = _lstm_train_args(captions, lens, keep_mask, I)
+    dev = captions.device
+    d_w_ih = torch.empty((2, G, I), dtype=_F32, device=dev)
+    d_w_hh = torch.empty((2, G, H), dtype=_F32, device=dev)
+    d_b_ih = torch.empty((2, G), dtype=_F32, device=dev)
+    d_b_hh = torch.empty((2, G), dtype=_F32, device=dev)
+    d_table = torch.empty((int(ntoken), I), dtype=_F32, device=dev)
+    _lib.call("objgan_lstm_bidir_backward", _p(None if d_out is None else _c(d_out)),
+              _p(None if d_hn is None else _c(d_hn)), _p(captions), _p(lens), _p(keep_mask), float(scale), _p(_c(w_ih)),
+              _p(_c(w_hh)), _p(ws), ws.numel(), _p(d_w_ih), _p(d_w_hh), _p(d_b_ih), _p(d_b_hh), _p(d_table),
+              B, L, int(max_len), I, H, int(ntoken), _stream())
+    return d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_table
+
+
+class _LstmBidirTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, wi0, wi1, wh0, wh1, bi0, bi1, bh0, bh1, captions, lens, max_len, keep_mask, scale):
+        w_ih, w_hh = torch.stack((wi0, wi1)), torch.stack((wh0, wh1))
+        out, hn, ws = lstm_bidir_train_forward(table, captions, lens, w_ih.transpose(1, 2).contiguous(),
+                                               w_hh.transpose(1, 2).contiguous(), torch.stack((bi0, bi1)),
+                                               torch.stack((bh0, bh1)), max_len, keep_mask, scale)
+        ctx.save_for_backward(captions, lens, keep_mask, w_ih, w_hh, ws)
+        ctx.meta = (table.shape[0], int(max_len), float(scale))
+        return out, hn
+
+    @staticmethod
+    def backward(ctx, d_out, d_hn):
+        captions, lens, keep_mask, w_ih, w_hh, ws = ctx.saved_tensors
+        ntoken, max_len, scale = ctx.meta
+        d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_table = lstm_bidir_backward(d_out, d_hn, captions, lens, w_ih, w_hh, ws,
+                                                                      ntoken, max_len, keep_mask, scale)
+        return (d_table, d_w_ih[0], d_w_ih[1], d_w_hh[0], d_w_hh[1], d_b_ih[0], d_b_ih[1], d_b_hh[0], d_b_hh[1],
+                None, None, None, None, None)
+
+
+def lstm_bidir_train(table, captions, lens, w_ih, w_hh, b_ih, b_hh, max_len, keep_mask=None, p=0.0):
+    """Embedding -> dropout (keep_mask uint8 [B, L, I], survivors scaled by 1 / (1 - p)) -> bidirectional LSTM over packed
+    captions, with gradients: w_ih, w_hh, b_ih, b_hh are the (forward, reverse) pairs of nn.LSTM's own tensors
+    (weight_ih_l0 [4H, I], weight_hh_l0 [4H, H], bias_* [4H]).  -> (words_emb [B, 2H, max_len], sent_emb [B, 2H]);
+    without a mask the values are bit for bit those of lstm_bidir_forward."""
+    if keep_mask is not None and not 0.0 <= p < 1.0:
+        raise _lib.ObjganHipError("lstm_bidir_train: dropout probability %r outside [0, 1)" % (p,))
+    scale = 1.0 / (1.0 - p) if keep_mask is not None else 1.0
+    return _LstmBidirTrainFn.apply(table, w_ih[0], w_ih[1], w_hh[0], w_hh[1], b_ih[0], b_ih[1], b_hh[0], b_hh[1],
+                                   captions, lens, int(max_len), keep_mask, scale)
+
+
+# ----------------------------------------------------------------------------------------------
 # box generator, sampling path
 # ----------------------------------------------------------------------------------------------
 def box_decode_cpw():
